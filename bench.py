@@ -11,6 +11,14 @@ cases, not bench lines.
 
 Usage:
   python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--keys K]
+                  [--dump-outputs DIR] [--full]
+A plain run does only what the headline figure needs: build the frame, warm
+up, time the K steps, print the line.  --full adds the legs that take runs of
+their own: the oracle parity gate before timing and the `cpu_baseline` leg
+(--no-verify / --no-cpu-baseline drop one of them again).  --dump-outputs DIR
+writes what the last timed step returned (group keys and per-group sums, as
+the caller's pandas frame holds them) to DIR/index_k.npy and DIR/v.npy in
+float64; inputs are seeded, so two builds can be compared output for output.
 N>1 is launched by the driver as one rank per GPU via torch.distributed.run;
 total rows stay fixed (the metric is quoted on 1e9 rows at 1/2/4/8 GPUs →
 "scaling": "strong"); the dense table all-reduce over RCCL/xGMI is the
@@ -23,7 +31,8 @@ groupby after frame build (per-key-column one-time work included: histogram,
 u32 key copy, key-range reduce — cached on the immutable column afterwards,
 the device analog of the reference's lazy metadata caches).  `cpu_baseline`
 times plain pandas groupby().sum() on this box's host cores (BASELINE.md
-§CPU-baseline), with the numpy oracle as the secondary figure.
+§CPU-baseline), with the numpy oracle as the secondary figure (--full only;
+null in a plain run).
 """
 
 from __future__ import annotations
@@ -42,6 +51,7 @@ sys.path.insert(0, REPO)
 HBM_PEAK = 8.0e12          # B/s, MI355X spec peak (MI355X_MICROARCH.md)
 ALG_BYTES_PER_ROW = 16     # 8 B key + 8 B value read per row
 SEED = 42
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs cap over all arrays
 
 
 def shard_seeds(rank: int):
@@ -160,6 +170,28 @@ def cpu_baseline_leg(keys_card: int, unit: str, dist: str):
     }
 
 
+def dump_outputs(out, directory: str):
+    """Write the result of the last timed step as float64 .npy arrays (group
+    keys under index_k, one array per value column).  A result over the size
+    cap is cut to a fixed seeded sample of its groups, same rows in every
+    array."""
+    pdf = out.to_pandas()
+    arrays = {"index_" + str(pdf.index.name or "k"): pdf.index.to_numpy()}
+    for c in pdf.columns:
+        arrays[str(c)] = pdf[c].to_numpy()
+    n = len(pdf)
+    cap = DUMP_MAX_BYTES // (8 * len(arrays))
+    sel = None
+    if n > cap:
+        sel = np.sort(np.random.default_rng(SEED).choice(n, cap,
+                                                         replace=False))
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a if sel is None else a[sel],
+                                 dtype=np.float64)
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -171,10 +203,19 @@ def main():
                     help="partitions per rank (scatter launches per step)")
     ap.add_argument("--dist", default="uniform",
                     help="key distribution: uniform | zipf1.2")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the oracle parity gate before timing and "
+                         "the cpu_baseline leg after it")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the cpu_baseline leg")
     ap.add_argument("--no-verify", action="store_true",
-                    help="skip the oracle parity gate before timing")
+                    help="with --full: skip the oracle parity gate")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result as "
+                         "DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import modin_amd.distributed as dmod
     from modin_amd.core import lib
@@ -209,7 +250,7 @@ def main():
     for _ in range(max(args.warmup - 1, 0)):
         step()
 
-    if world == 1 and not args.no_verify:
+    if args.full and world == 1 and not args.no_verify:
         # parity gate outside the timed region: the full result must match
         # the oracle regeneration of the same device draws
         res = step()._query_compiler._modin_frame
@@ -272,8 +313,10 @@ def main():
     value = args.rows * args.steps / elapsed if elapsed > 0 else 0.0
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(out, args.dump_outputs)
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline_leg(args.keys, "rows/s", args.dist)
         line = {
             "metric": "rows/sec groupby-sum",
