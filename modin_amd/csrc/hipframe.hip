@@ -47,6 +47,7 @@ struct hf_col {
   void*   d_hist = nullptr;
   int64_t hist_kmin = 0;
   int64_t hist_nb = 0;
+  int64_t hist_nslots = 0;       // exact n_slots the histogram was cut for
   // cached u32 shifted copy of an int64 key column (key - key_min), the
   // narrow-key fast path for the radix scatter (12 B/row instead of 16).
   // Same immutable-column caching rationale as d_hist.
@@ -60,6 +61,22 @@ struct hf_col {
   int64_t work_n = 0;
   int64_t radix_rows = 0;        // payload rows (64-aligned region total)
   int     radix_rl = 0;          // validity: matches (hist_kmin, hist_nb)
+  // cached scatter plan: every decision the radix scatter takes depends on
+  // the (immutable) key column alone, so the first radix call records them
+  // and later calls replay a pure value permutation that never reads keys
+  // (k_gb_replay).  One plan per column, valid for exactly
+  // (plan_kmin, plan_nslots, plan_rl) at GB_PLAN_TILE rows per tile; another
+  // geometry re-records.  Invalidated with d_hist (same derivation chain).
+  void*   d_plan_dst = nullptr;  // u16[n]: row -> slot in its tile's bucket-
+                                 // sorted LDS staging; 0xFFFF = key out of range
+  void*   d_plan_rk = nullptr;   // u16[radix_rows]: low-key stream P2 reads
+  void*   d_plan_tab = nullptr;  // u32[ntiles][2*nb+1]: tile bucket offsets
+                                 // (nb+1, last = staged rows) + region bases
+  void*   d_plan_meta = nullptr; // u64[2]: region slot of the odd tail row
+                                 // (~0 = none), out-of-range rows recorded
+  int64_t plan_kmin = 0;
+  int64_t plan_nslots = 0;
+  int     plan_rl = 0;           // 0 = no plan
 };
 
 namespace {
@@ -247,6 +264,17 @@ inline hipError_t dev_free(void* p, hipStream_t s) {
   if (sync_alloc()) { hipStreamSynchronize(s); return hipFree(p); }
   g_cache.free(p);
   return hipSuccess;
+}
+
+// drop a key column's cached scatter plan (see hf_col)
+void plan_free(hf_col* c) {
+  void** bufs[4] = {&c->d_plan_dst, &c->d_plan_rk, &c->d_plan_tab,
+                    &c->d_plan_meta};
+  for (void** b : bufs) {
+    if (*b) dev_free(*b, g.stream);
+    *b = nullptr;
+  }
+  c->plan_rl = 0;
 }
 }  // namespace
 
@@ -668,7 +696,12 @@ __global__ void __launch_bounds__(BLOCK) k_gb_accum(
 //                        8 B val + 2 B lowkey into exact per-bucket regions
 //                        (LDS ranks, one global cursor atomic per
 //                        block-tile per bucket); software-pipelined across
-//                        tiles (round 2)
+//                        tiles (round 2).  Its decisions depend on the keys
+//                        alone, so by default the first call RECORDS them as
+//                        a plan on the key column and later calls run
+//      k_gb_replay     : the recorded value permutation — read 2 B dst +
+//                        8 B val, write 8 B val per row; no key reads, no
+//                        atomics (P2 reads the low keys from the plan)
 //   P2 k_gb_bucket_agg : stream each bucket chunk into an LDS table
 //                        (ds_add_f64 behind a register run-accumulator for
 //                        skewed keys), merge non-empty slots into the
@@ -736,7 +769,17 @@ __global__ void __launch_bounds__(BLOCK) k_conv_keys32(
 // wave-parked stall of the round-1 kernel, profiles/r01b/sq_scatter.txt).
 // row0/row1 bound the input rows (the overlapped-P2 path scatters in
 // chunks; row0 is always even, only the LAST chunk may end odd)
-template <int NV, int RPT, int BLK, int RL, bool K32>
+// REC: the plan-recording variant (first radix call on a key column).  Same
+// work, plus it keeps what a replay needs: each row's staging slot (`dst`,
+// one coalesced ushort2 per row pair), the tile's offset/base table row, the
+// tail row's region slot and the out-of-range count.
+struct GbPlanRec {
+  unsigned short* dst;
+  unsigned* tab;
+  unsigned long long* meta;
+};
+
+template <int NV, int RPT, int BLK, int RL, bool K32, bool REC = false>
 __global__ void __launch_bounds__(BLK) k_gb_scatter(
     const int64_t* __restrict__ keys, const unsigned* __restrict__ keys32,
     const double* __restrict__ v0,
@@ -744,9 +787,11 @@ __global__ void __launch_bounds__(BLK) k_gb_scatter(
     int64_t key_min, int64_t n_slots,
     int nb, unsigned* __restrict__ cursors,
     double* __restrict__ r0, double* __restrict__ r1,
-    unsigned short* __restrict__ rk, unsigned long long* __restrict__ err) {
+    unsigned short* __restrict__ rk, unsigned long long* __restrict__ err,
+    GbPlanRec rec) {
   constexpr int TILE = BLK * RPT;
   constexpr int PAIRS = RPT / 2;
+  static_assert(!REC || TILE < 0xFFFF, "plan dst is u16 with 0xFFFF reserved");
   if ((row1 & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
     // odd tail row: direct single-row reservation + write
     const int64_t k =
@@ -757,8 +802,10 @@ __global__ void __launch_bounds__(BLK) k_gb_scatter(
       rk[pos] = (unsigned short)(k & ((1 << RL) - 1));
       if (NV > 0) r0[pos] = v0[row1 - 1];
       if (NV > 1) r1[pos] = v1[row1 - 1];
+      if (REC) rec.meta[0] = (unsigned long long)pos;
     } else {
       atomicAdd(err, 1ULL);
+      if (REC) atomicAdd(&rec.meta[1], 1ULL);
     }
   }
   const int64_t pr0 = row0 >> 1;
@@ -820,12 +867,14 @@ __global__ void __launch_bounds__(BLK) k_gb_scatter(
           lk[a] = (unsigned)(ka & ((1 << RL) - 1));
         } else {
           atomicAdd(err, 1ULL);
+          if (REC) atomicAdd(&rec.meta[1], 1ULL);
         }
         if ((uint64_t)kb < (uint64_t)n_slots) {
           lb[bslot] = (int)(kb >> RL);
           lk[bslot] = (unsigned)(kb & ((1 << RL) - 1));
         } else {
           atomicAdd(err, 1ULL);
+          if (REC) atomicAdd(&rec.meta[1], 1ULL);
         }
       }
     }
@@ -865,7 +914,32 @@ __global__ void __launch_bounds__(BLK) k_gb_scatter(
         if (NV > 1) sval1[p] = (j & 1) ? vraw1[j >> 1].y : vraw1[j >> 1].x;
       }
     }
+    if (REC) {
+      // row0 == 0 on the plan path, so pair pj of the tile is input pair pj
+#pragma unroll
+      for (int j = 0; j < PAIRS; ++j) {
+        const int64_t pj = tile * (TILE / 2) + (int64_t)j * BLK + threadIdx.x;
+        if (pj < npair_total) {
+          const int a = 2 * j, bslot = 2 * j + 1;
+          ushort2 d;
+          d.x = lb[a] >= 0 ? (unsigned short)(it_off[lb[a]] + lr[a]) : 0xFFFF;
+          d.y = lb[bslot] >= 0
+                    ? (unsigned short)(it_off[lb[bslot]] + lr[bslot])
+                    : 0xFFFF;
+          reinterpret_cast<ushort2*>(rec.dst)[pr0 + pj] = d;
+        }
+      }
+    }
     __syncthreads();  // staging visible; it_cnt reads (scan) long done
+    if (REC) {
+      // the tile's table row (it_gbase of an empty bucket is never read)
+      unsigned* row = rec.tab + tile * (2 * (int64_t)nb + 1);
+      for (int t = threadIdx.x; t < nb; t += blockDim.x) {
+        row[t] = it_off[t];
+        row[nb + 1 + t] = it_cnt[t] ? it_gbase[t] : 0u;
+      }
+      if (threadIdx.x == 0) row[nb] = *s_total;
+    }
     // registers are dead — issue the NEXT tile's loads so they fly during
     // this tile's writeout, and clear it_cnt for the next rank phase
     const int64_t nxt = tile + gridDim.x;
@@ -882,6 +956,119 @@ __global__ void __launch_bounds__(BLK) k_gb_scatter(
     // loop-top barrier orders the writeout's LDS reads against the next
     // tile's staging writes
   }
+}
+
+// Plan geometry: the 1024x12 tile of the single-column scatter, for every
+// nvals (one plan serves all value-column counts).
+constexpr int GB_PLAN_BLK = 1024;
+constexpr int GB_PLAN_RPT = 12;
+constexpr int GB_PLAN_TILE = GB_PLAN_BLK * GB_PLAN_RPT;
+
+// P1 steady state: replay a recorded plan as a pure value permutation, one
+// value column per launch.  Reads 2 B dst + 8 B value per row, writes 8 B;
+// no key reads, no LDS atomics, no scan, no global atomics.  Same software
+// pipelining as k_gb_scatter: the next tile's loads (dst, values and table
+// row) are issued right after this tile's staging.
+// The writeout recovers the bucket b of a staged slot p from the tile's
+// offsets alone: b = the last bucket with it_off[b] <= p, found by a
+// fixed-trip binary search per slot.  The RPT searches of a thread are
+// independent and unrolled side by side, so their LDS reads overlap; work
+// is split by slot, never by bucket, so a zipf head bucket that fills most
+// of a tile costs nothing extra.
+template <int RPT, int BLK>
+__global__ void __launch_bounds__(BLK) k_gb_replay(
+    const unsigned short* __restrict__ dst, const double* __restrict__ v,
+    int64_t n, int nb, int search0, const unsigned* __restrict__ tab,
+    const unsigned long long* __restrict__ meta, double* __restrict__ r0,
+    unsigned long long* __restrict__ err, int add_err) {
+  constexpr int TILE = BLK * RPT;
+  constexpr int PAIRS = RPT / 2;
+  constexpr int TABR = 3;  // table row is 2*nb+1 <= 2049 words <= 3 per thread
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (n & 1) {
+      const unsigned long long pos = meta[0];
+      if (pos != ~0ULL) r0[pos] = v[n - 1];
+    }
+    // out-of-range keys were counted while recording; every call reports them
+    const unsigned long long oor = meta[1];
+    if (add_err && oor) atomicAdd(err, oor);
+  }
+  const int64_t npair_total = n >> 1;
+  const int64_t ntiles = (npair_total * 2 + TILE - 1) / TILE;
+  const int tabw = 2 * nb + 1;
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  double* sval = reinterpret_cast<double*>(smem_raw);         // [TILE]
+  unsigned* it_off = reinterpret_cast<unsigned*>(sval + TILE);  // [nb + 1]
+  const unsigned* it_gbase = it_off + nb + 1;                   // [nb]
+
+  unsigned draw[PAIRS];
+  double2 vraw[PAIRS];
+  unsigned traw[TABR];
+  auto issue_loads = [&](int64_t tile) {
+#pragma unroll
+    for (int j = 0; j < PAIRS; ++j) {
+      const int64_t pj = tile * (TILE / 2) + (int64_t)j * BLK + threadIdx.x;
+      if (pj < npair_total) {
+        draw[j] = reinterpret_cast<const unsigned*>(dst)[pj];
+        vraw[j] = reinterpret_cast<const double2*>(v)[pj];
+      }
+    }
+    const unsigned* row = tab + tile * (int64_t)tabw;
+#pragma unroll
+    for (int j = 0; j < TABR; ++j) {
+      const int t = j * BLK + threadIdx.x;
+      if (t < tabw) traw[j] = row[t];
+    }
+  };
+
+  int64_t tile = blockIdx.x;
+  if (tile < ntiles) issue_loads(tile);
+  for (; tile < ntiles; tile += gridDim.x) {
+    __syncthreads();  // previous tile's writeout is done with sval / table
+#pragma unroll
+    for (int j = 0; j < PAIRS; ++j) {
+      const int64_t pj = tile * (TILE / 2) + (int64_t)j * BLK + threadIdx.x;
+      if (pj < npair_total) {
+        const unsigned pa = draw[j] & 0xFFFFu, pb = draw[j] >> 16;
+        if (pa < (unsigned)TILE) sval[pa] = vraw[j].x;
+        if (pb < (unsigned)TILE) sval[pb] = vraw[j].y;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < TABR; ++j) {
+      const int t = j * BLK + threadIdx.x;
+      if (t < tabw) it_off[t] = traw[j];
+    }
+    __syncthreads();  // staging + table visible
+    const int64_t nxt = tile + gridDim.x;
+    if (nxt < ntiles) issue_loads(nxt);
+    const int staged = (int)it_off[nb];
+    int b[RPT];
+#pragma unroll
+    for (int j = 0; j < RPT; ++j) b[j] = 0;
+    // it_off[0] == 0 <= p, and it_off[nb] == staged > p bounds the answer
+    for (int s = search0; s > 0; s >>= 1) {
+#pragma unroll
+      for (int j = 0; j < RPT; ++j) {
+        const int p = j * BLK + threadIdx.x;
+        const int m = b[j] + s;
+        if (p < staged && m < nb && it_off[m] <= (unsigned)p) b[j] = m;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < RPT; ++j) {
+      const int p = j * BLK + threadIdx.x;
+      if (p < staged)
+        r0[(int64_t)it_gbase[b[j]] + ((unsigned)p - it_off[b[j]])] = sval[p];
+    }
+  }
+}
+
+// nvals == 0 on a recorded plan runs no P1 at all; this carries the recorded
+// out-of-range count to the shared error word so compaction still raises.
+__global__ void k_gb_plan_err(const unsigned long long* __restrict__ meta,
+                              unsigned long long* __restrict__ err) {
+  if (blockIdx.x == 0 && threadIdx.x == 0 && meta[1]) atomicAdd(err, meta[1]);
 }
 
 // Build P2 work items ON DEVICE from cursor snapshots (the overlapped
@@ -2426,6 +2613,7 @@ int hf_col_free(hf_col* col) {
   if (g.inited && col->d_k32) dev_free(col->d_k32, g.stream);
   if (g.inited && col->d_curinit) dev_free(col->d_curinit, g.stream);
   if (g.inited && col->d_work) dev_free(col->d_work, g.stream);
+  if (g.inited) plan_free(col);
   delete col;
   return HF_OK;
 }
@@ -2657,10 +2845,15 @@ namespace {
 // hf_col — repeated groupbys on the same keys skip the P0 pass entirely.
 int ensure_host_hist(hf_col* keys, int64_t key_min, int64_t n_slots,
                      int64_t nb, int range_log) {
-  if (keys->d_hist && keys->hist_kmin == key_min && keys->hist_nb == nb)
+  // keyed on the exact n_slots, not only the bucket count: rows between two
+  // n_slots inside the same last bucket change that bucket's region size
+  if (keys->d_hist && keys->hist_kmin == key_min && keys->hist_nb == nb &&
+      keys->hist_nslots == n_slots)
     return HF_OK;
   if (keys->d_hist) { free(keys->d_hist); keys->d_hist = nullptr; }
-  // the radix layout cache derives from this histogram: invalidate with it
+  // the radix layout cache and the scatter plan derive from this histogram:
+  // invalidate with it
+  plan_free(keys);
   if (keys->d_curinit) {
     dev_free(keys->d_curinit, g.stream);
     keys->d_curinit = nullptr;
@@ -2688,6 +2881,7 @@ int ensure_host_hist(hf_col* keys, int64_t key_min, int64_t n_slots,
   keys->d_hist = h;
   keys->hist_kmin = key_min;
   keys->hist_nb = nb;
+  keys->hist_nslots = n_slots;
   return HF_OK;
 }
 
@@ -2756,8 +2950,6 @@ int gb_radix_path(hf_col* keys, const GbPtrs& ptrs, int nvals, int64_t key_min,
   const int64_t nb = (n_slots + (1 << RL) - 1) >> RL;
   int rc = ensure_host_hist(keys, key_min, n_slots, nb, RL);
   if (rc != HF_OK) return rc;
-  rc = ensure_keys32(keys, key_min);
-  if (rc != HF_OK) return rc;
   const int64_t* h = keys->d_hist ? (const int64_t*)keys->d_hist : nullptr;
   // exact per-bucket regions, 64-row aligned; u32 cursors cap one partition
   // at ~4.29e9 rows (shard larger frames).  The cursor-init array and the
@@ -2811,19 +3003,65 @@ int gb_radix_path(hf_col* keys, const GbPtrs& ptrs, int nvals, int64_t key_min,
   }
   const int64_t off = keys->radix_rows;
   GbWorkItem* d_work = (GbWorkItem*)keys->d_work;
+  const int64_t alloc_rows = off > 0 ? off : 64;
+  // HF_GB_PLAN=0 / HF_GB_OVERLAP=1 are read once; either selects the
+  // plan-less path below
+  static const bool plan_env = [] {
+    const char* e = getenv("HF_GB_PLAN");
+    return !(e && e[0] == '0');
+  }();
+  static const bool overlap_env = [] {
+    const char* e = getenv("HF_GB_OVERLAP");
+    return e && e[0] == '1';
+  }();
+  // ---- scatter plan (see hf_col): valid -> replay, else record now.  A
+  // failed plan allocation falls back to the plan-less path, never fails
+  // the call.
+  bool use_plan = plan_env && !overlap_env;
+  const bool plan_valid = use_plan && keys->plan_rl == RL &&
+                          keys->plan_kmin == key_min &&
+                          keys->plan_nslots == n_slots;
+  const int64_t plan_tiles =
+      ((n & ~1LL) + GB_PLAN_TILE - 1) / GB_PLAN_TILE;
+  const int64_t plan_tabw = 2 * nb + 1;
+  if (use_plan && !plan_valid) {
+    plan_free(keys);
+    const bool ok =
+        dev_alloc(&keys->d_plan_dst, std::max<int64_t>(n & ~1LL, 2) * 2,
+                  g.stream) == hipSuccess &&
+        dev_alloc(&keys->d_plan_rk, alloc_rows * 2, g.stream) == hipSuccess &&
+        dev_alloc(&keys->d_plan_tab,
+                  std::max<int64_t>(plan_tiles, 1) * plan_tabw * 4,
+                  g.stream) == hipSuccess &&
+        dev_alloc(&keys->d_plan_meta, 16, g.stream) == hipSuccess;
+    if (!ok) {
+      (void)hipGetLastError();
+      plan_free(keys);
+      use_plan = false;
+    }
+  }
+  if (!use_plan) {
+    rc = ensure_keys32(keys, key_min);
+    if (rc != HF_OK) return rc;
+  }
+  const bool record = use_plan && !plan_valid;
   double* r0 = nullptr;
   double* r1 = nullptr;
   unsigned short* rk = nullptr;
   unsigned* d_cur = nullptr;
-  const int64_t alloc_rows = off > 0 ? off : 64;
   if (nvals > 0)
     HF_HIP("gb_radix", dev_alloc((void**)&r0, alloc_rows * 8, g.stream));
-  if (nvals > 1)
+  if (nvals > 1 && !use_plan)
     HF_HIP("gb_radix", dev_alloc((void**)&r1, alloc_rows * 8, g.stream));
-  HF_HIP("gb_radix", dev_alloc((void**)&rk, alloc_rows * 2, g.stream));
-  HF_HIP("gb_radix", dev_alloc((void**)&d_cur, nb * 4, g.stream));
-  HF_HIP("gb_radix", hipMemcpyAsync(d_cur, keys->d_curinit, nb * 4,
-                                    hipMemcpyDeviceToDevice, g.stream));
+  if (use_plan)
+    rk = (unsigned short*)keys->d_plan_rk;
+  else
+    HF_HIP("gb_radix", dev_alloc((void**)&rk, alloc_rows * 2, g.stream));
+  if (!use_plan || record) {
+    HF_HIP("gb_radix", dev_alloc((void**)&d_cur, nb * 4, g.stream));
+    HF_HIP("gb_radix", hipMemcpyAsync(d_cur, keys->d_curinit, nb * 4,
+                                      hipMemcpyDeviceToDevice, g.stream));
+  }
 
   // ---- overlapped path: scatter in 4 chunks on the main stream; after
   // each chunk the consumer stream aggregates the region slices that
@@ -2833,10 +3071,6 @@ int gb_radix_path(hf_col* keys, const GbPtrs& ptrs, int nvals, int64_t key_min,
   // each phase runs ~1.5x slower (uniform 9.2 ms vs 7.0 serial) — the
   // overlap never recovers the loss.  Kept behind HF_GB_OVERLAP=1 for
   // future experiments; default is the serial two-phase path.
-  static const bool overlap_env = [] {
-    const char* e = getenv("HF_GB_OVERLAP");
-    return e && e[0] == '1';
-  }();
   const bool overlap =
       overlap_env && n >= (64LL << 20) && nvals <= 2 && nb <= 1024;
   if (overlap) {
@@ -2870,7 +3104,8 @@ int gb_radix_path(hf_col* keys, const GbPtrs& ptrs, int nvals, int64_t key_min,
                            (const int64_t*)keys->dptr,
                            (const unsigned*)keys->d_k32, ptrs.vals[0],
                            ptrs.vals[1], bounds[c], bounds[c + 1], key_min,
-                           n_slots, (int)nb, d_cur, r0, r1, rk, d_err);
+                           n_slots, (int)nb, d_cur, r0, r1, rk, d_err,
+                           GbPlanRec{});
       });
     };
     // per-chunk device work items (k_gb_make_work) + the regular
@@ -2979,18 +3214,72 @@ int gb_radix_path(hf_col* keys, const GbPtrs& ptrs, int nvals, int64_t key_min,
                          (const int64_t*)keys->dptr,
                          (const unsigned*)keys->d_k32, ptrs.vals[0],
                          ptrs.vals[1], (int64_t)0, n, key_min, n_slots,
-                         (int)nb, d_cur, r0, r1, rk, d_err);
+                         (int)nb, d_cur, r0, r1, rk, d_err, GbPlanRec{});
     });
   };
-  rc = nvals == 0 ? scat(std::integral_constant<int, 0>{},
-                         std::integral_constant<int, 12>{},
-                         std::integral_constant<int, 1024>{})
-       : nvals == 1 ? scat(std::integral_constant<int, 1>{},
+  // plan path P1.  Record: the scatter itself on the int64 keys (no u32
+  // copy), first value column only, keeping its decisions on the hf_col.
+  // Replay: the value permutation, into the one r0 every column reuses.
+  auto plan_record = [&](auto nvTag) {
+    constexpr int NVv = decltype(nvTag)::value;
+    const uint32_t sgrid =
+        (uint32_t)std::min<int64_t>(std::max<int64_t>(plan_tiles, 1), 2048);
+    const uint32_t lds =
+        (uint32_t)((int64_t)GB_PLAN_TILE * (8 * NVv + 4) + nb * 12 + 16);
+    unsigned long long* meta = (unsigned long long*)keys->d_plan_meta;
+    HF_HIP("gb_radix", hipMemsetAsync(meta, 0xFF, 8, g.stream));
+    HF_HIP("gb_radix", hipMemsetAsync(meta + 1, 0, 8, g.stream));
+    int r = timed_launch("gb_plan_record", [&] {
+      hipLaunchKernelGGL(
+          (k_gb_scatter<NVv, GB_PLAN_RPT, GB_PLAN_BLK, RL, false, true>),
+          dim3(sgrid), dim3(GB_PLAN_BLK), lds, g.stream,
+          (const int64_t*)keys->dptr, (const unsigned*)nullptr, ptrs.vals[0],
+          (const double*)nullptr, (int64_t)0, n, key_min, n_slots, (int)nb,
+          d_cur, r0, (double*)nullptr, rk, d_err,
+          GbPlanRec{(unsigned short*)keys->d_plan_dst,
+                    (unsigned*)keys->d_plan_tab, meta});
+    });
+    if (r != HF_OK) return r;
+    keys->plan_kmin = key_min;
+    keys->plan_nslots = n_slots;
+    keys->plan_rl = RL;
+    return (int)HF_OK;
+  };
+  int search0 = 0;  // largest power of two <= nb - 1 (replay's first step)
+  for (int s = 1; s <= nb - 1; s <<= 1) search0 = s;
+  auto plan_replay = [&](const double* v, bool add_err) {
+    const uint32_t sgrid =
+        (uint32_t)std::min<int64_t>(std::max<int64_t>(plan_tiles, 1), 2048);
+    const uint32_t lds =
+        (uint32_t)((int64_t)GB_PLAN_TILE * 8 + plan_tabw * 4);
+    return timed_launch("gb_scatter", [&] {
+      hipLaunchKernelGGL((k_gb_replay<GB_PLAN_RPT, GB_PLAN_BLK>), dim3(sgrid),
+                         dim3(GB_PLAN_BLK), lds, g.stream,
+                         (const unsigned short*)keys->d_plan_dst, v, n,
+                         (int)nb, search0, (const unsigned*)keys->d_plan_tab,
+                         (const unsigned long long*)keys->d_plan_meta, r0,
+                         d_err, add_err ? 1 : 0);
+    });
+  };
+  if (!use_plan) {
+    rc = nvals == 0 ? scat(std::integral_constant<int, 0>{},
                            std::integral_constant<int, 12>{},
                            std::integral_constant<int, 1024>{})
-                    : scat(std::integral_constant<int, 2>{},
-                           std::integral_constant<int, 12>{},
-                           std::integral_constant<int, 512>{});
+         : nvals == 1 ? scat(std::integral_constant<int, 1>{},
+                             std::integral_constant<int, 12>{},
+                             std::integral_constant<int, 1024>{})
+                      : scat(std::integral_constant<int, 2>{},
+                             std::integral_constant<int, 12>{},
+                             std::integral_constant<int, 512>{});
+  } else if (record) {
+    rc = nvals == 0 ? plan_record(std::integral_constant<int, 0>{})
+                    : plan_record(std::integral_constant<int, 1>{});
+  } else if (nvals == 0) {
+    rc = timed_launch("gb_plan_err", [&] {
+      hipLaunchKernelGGL(k_gb_plan_err, dim3(1), dim3(64), 0, g.stream,
+                         (const unsigned long long*)keys->d_plan_meta, d_err);
+    });
+  }
   if (rc != HF_OK) return rc;
   // P2 aggregate, one column per launch
   const bool cnt = counts != 0;
@@ -3012,7 +3301,13 @@ int gb_radix_path(hf_col* keys, const GbPtrs& ptrs, int nvals, int64_t key_min,
       rc = agg(T{}, F{}, F{}, nullptr, nullptr, nullptr);
     } else {
       for (int c = 0; c < nvals && rc == HF_OK; ++c) {
-        const double* v = c == 0 ? r0 : r1;
+        // plan path: replay(column) -> agg(column) through the one r0; the
+        // record pass has already scattered column 0
+        if (use_plan && !(record && c == 0)) {
+          rc = plan_replay(ptrs.vals[c], !record && c == 0);
+          if (rc != HF_OK) break;
+        }
+        const double* v = (c == 0 || use_plan) ? r0 : r1;
         double* gs = (double*)sums + (int64_t)c * n_slots;
         unsigned long long* gc =
             cnt ? (unsigned long long*)counts + (int64_t)c * n_slots : nullptr;
@@ -3024,11 +3319,18 @@ int gb_radix_path(hf_col* keys, const GbPtrs& ptrs, int nvals, int64_t key_min,
                    : agg(F{}, F{}, T{}, v, gs, gc);
       }
     }
+  } else if (use_plan && !record && nvals > 0) {
+    // no in-range row at all: nothing to permute, but the recorded
+    // out-of-range count still has to reach the error word
+    rc = timed_launch("gb_plan_err", [&] {
+      hipLaunchKernelGGL(k_gb_plan_err, dim3(1), dim3(64), 0, g.stream,
+                         (const unsigned long long*)keys->d_plan_meta, d_err);
+    });
   }
   if (r0) dev_free(r0, g.stream);
   if (r1) dev_free(r1, g.stream);
-  dev_free(rk, g.stream);
-  dev_free(d_cur, g.stream);
+  if (!use_plan) dev_free(rk, g.stream);
+  if (d_cur) dev_free(d_cur, g.stream);
   return rc;
 }
 
