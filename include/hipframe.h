@@ -173,6 +173,28 @@ int hf_groupby_accum(const hf_col* keys,            /* HF_INT64, len n        */
                      int64_t key_min, int64_t n_slots,
                      uintptr_t sums, uintptr_t rowcnt, uintptr_t counts);
 
+/* ---- Fused group moments: the centred second pass of groupby skew and of
+ * frame skew/kurt.  The reference's skew map/reduce
+ * (storage_formats/pandas/groupby.py:116-182) sums x, x², x³ and expands the
+ * centred moments from them, which cancels once mean/std is large; frame
+ * skew/kurt are bound as Reduce (storage_formats/pandas/query_compiler.py:
+ * 1144-1152).  Here the caller supplies a per-group centre (its pass-1 mean)
+ * and one pass accumulates powers of d = x − centre[gid] into a raw table
+ *   table : double[6][n_groups]   Σd, Σd², Σd³, Σd⁴, min x, max x
+ * that the caller initialises to 0, 0, 0, 0, +inf, −inf; calls accumulate, so
+ * several partitions feed one table (as hf_groupby_accum).  min == max is the
+ * exact constant-group test (pandas returns 0.0 there).
+ *   gid    : group of each row in [0, n_groups); negative = row skipped;
+ *            NULL = every row is group 0 (n_groups must be 1)
+ *   val    : NaN rows are skipped
+ *   centre : device double[n_groups]
+ * A gid >= n_groups is never indexed: such rows are counted and the call
+ * returns HF_ERR_ARG.  n_groups <= 1024 aggregates in block-private LDS
+ * tables, larger group counts use device-scope atomics on the table. */
+int hf_group_moments(const hf_col* gid,             /* HF_INT64 len n or NULL */
+                     const hf_col* val,             /* HF_FLOAT64, len n      */
+                     uintptr_t centre, int64_t n_groups, uintptr_t table);
+
 int hf_fill_f64(uintptr_t dptr, double value, int64_t n);
 int hf_fill_i64(uintptr_t dptr, int64_t value, int64_t n);
 

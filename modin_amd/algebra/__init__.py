@@ -167,12 +167,30 @@ class GroupByReduce(Operator):
       count -> same kernels, value counts
       mean  -> sums/counts division on the compacted columns (:87-113 shape)
       min/max -> ds/global f64 min/max tables; empty groups fixed to NaN
+    and the three entries that need a second pass or a pre-map (TWO_PASS):
+      skew  -> sum pass for the group means, then the fused centred-moments
+               kernel (hf_group_moments) — (:116-182) without the raw
+               power-sum cancellation
+      any/all -> truth test x != 0 through the max / min tables
+    prod, the table's tenth entry, is composed in HipDataframe.groupby_prod.
     """
 
     SUPPORTED = ("sum", "count", "mean", "min", "max")
+    TWO_PASS = ("skew", "any", "all")
 
     @classmethod
     def register(cls, agg: str):
+        if agg in cls.TWO_PASS:
+            def caller2(query_compiler, by, dropna: bool = True, **kwargs):
+                frame = query_compiler._modin_frame
+                if agg == "skew":
+                    result = frame.groupby_skew(by)
+                else:
+                    result = frame.groupby_anyall(by, agg == "all",
+                                                  dropna=dropna)
+                return query_compiler.__constructor__(result)
+
+            return caller2
         if agg not in cls.SUPPORTED:
             raise lib.HfError(
                 f"groupby agg {agg!r} not implemented (round-1 supports "

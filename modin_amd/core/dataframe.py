@@ -762,6 +762,241 @@ class HipDataframe:
         k = len(val_names)
         return keys, key_cats, sums[:k], sums[k:], counts[:k], n
 
+    @staticmethod
+    def _single_rank_only(op: str) -> None:
+        from ..distributed import is_active
+        if is_active():
+            raise lib.HfError(f"{op} at world>1 is a later round")
+
+    def groupby_skew(self, by) -> "HipDataframe":
+        """groupby skew (GroupbyReduceImpl's skew entry,
+        storage_formats/pandas/groupby.py:116-182), two passes: the
+        existing SUM pass gives keys, Σx and counts, so centre = Σx/n per
+        group; hf_group_moments then accumulates powers of d = x − centre
+        per group.  The centre is itself rounded, so with e = Σd/n
+          m2 = Σd² − n e²,  m3 = Σd³ − 3e Σd² + 2n e³,
+          skew = n √(n−1)/(n−2) · m3 / m2^1.5,
+        exactly 0.0 where min == max (a constant group) and NaN where
+        n < 3 (pandas group_skew)."""
+        self._single_rank_only("groupby skew")
+        if isinstance(by, (list, tuple)):
+            if len(by) == 1:
+                by = by[0]
+            else:
+                cf, decode = self._combined_key_frame(list(by))
+                keep = [c for c in cf.columns if c not in by]
+                res = cf.take_columns(keep).groupby_skew(self.KEYCOL)
+                res._index = decode(lib.get(res._index.col))
+                return res
+        val_names = [c for c in self.columns if c != by]
+        blk_cats = (self._partitions[0].block().cats
+                    if self._partitions else {})
+        bad = [v for v in val_names if v in blk_cats]
+        if bad:
+            raise lib.HfError(f"groupby skew over string column(s) {bad}")
+        key_cats = blk_cats.get(by)
+        parts = self._partitions
+        float_key = (parts and key_cats is None
+                     and parts[0].block().columns[by].dtype_code
+                     == lib.HF_FLOAT64)
+        fparts = []
+        for p in parts:
+            block = p.block()
+            kc = block.columns[by]
+            cols = {by: kc}
+            for v in val_names:
+                cols[v] = lib.cast_f64(block.columns[v])
+            mask = None
+            if float_key:
+                # NaN keys drop (pandas dropna=True); valid float keys ride
+                # the ordered f64->i64 transform as in groupby_reduce
+                if kc.length and lib.reduce(kc).count < kc.length:
+                    mask = lib.compare_scalar(lib.CMP_NOTNA, kc, 0.0)
+            elif key_cats is not None:
+                if kc.length and lib.reduce(kc).imn < 0:
+                    mask = lib.compare_scalar(lib.CMP_GE, kc, 0.0)
+            if mask is not None:
+                plan = lib.filter_plan(mask)
+                cols = {m: lib.filter_apply(plan, c)
+                        for m, c in cols.items()}
+            if float_key:
+                cols[by] = lib.ordered_i64(cols[by])
+            fparts.append(HipDataframePartition(
+                DeviceBlock(cols, cols[by].length, block.cats)))
+        # pass 1: keys (sorted distinct), Σx, non-NaN counts
+        keys, sums, counts, n, _biases = \
+            self._partition_mgr_cls.groupby_reduce(
+                fparts, by, val_names, True, lib.AGG_SUM)
+        cols = {}
+        if n == 0:
+            for name in val_names:
+                cols[name] = lib.alloc(0, lib.HF_FLOAT64)
+        else:
+            cnt_f = [lib.cast_f64(c) for c in counts]
+            centres = [lib.binary(lib.BIN_DIV, sums[i], cnt_f[i])
+                       for i in range(len(val_names))]
+            tables = [lib.group_moments_table(n) for _ in val_names]
+            # pass 2: one group id per row (−1 for keys pass 1 dropped),
+            # shared by every value column of the partition
+            for p in fparts:
+                block = p.block()
+                if not block.length:
+                    continue
+                gid = lib.search_sorted(block.columns[by], keys)
+                for i, name in enumerate(val_names):
+                    lib.group_moments(gid, block.columns[name], centres[i],
+                                      n, tables[i])
+            for i, name in enumerate(val_names):
+                cols[name] = self._skew_from_table(tables[i], counts[i],
+                                                   cnt_f[i], n)
+        part = HipDataframePartition(DeviceBlock(cols, n))
+        dtypes = pandas.Series({v: np.dtype(np.float64) for v in val_names})
+        if float_key:
+            idx = pandas.Index(lib.ordered_to_f64_np(lib.get(keys)), name=by)
+        else:
+            idx = DeviceIndex(keys, name=by, cats=key_cats)
+        return HipDataframe([part], idx, val_names, [n], dtypes)
+
+    @staticmethod
+    def _skew_from_table(table, cnt, cnt_f, n):
+        """Device finish of groupby_skew over one hf_group_moments table."""
+        B, M = lib.binary, lib.map_scalar
+        s1, s2, s3, mn, mx = (lib.col_slice(table, r * n, n)
+                              for r in (lib.GM_S1, lib.GM_S2, lib.GM_S3,
+                                        lib.GM_MIN, lib.GM_MAX))
+        e = B(lib.BIN_DIV, s1, cnt_f)
+        s1e = B(lib.BIN_MUL, s1, e)                       # n e²
+        m2 = B(lib.BIN_SUB, s2, s1e)
+        m3 = B(lib.BIN_ADD,
+               B(lib.BIN_SUB, s3,
+                 M(lib.MAP_MUL, B(lib.BIN_MUL, e, s2), 3.0)),
+               M(lib.MAP_MUL, B(lib.BIN_MUL, s1e, e), 2.0))
+        scale = B(lib.BIN_DIV,
+                  B(lib.BIN_MUL, cnt_f,
+                    M(lib.MAP_SQRT, M(lib.MAP_ADD, cnt_f, -1.0), 0.0)),
+                  M(lib.MAP_ADD, cnt_f, -2.0))
+        sk = B(lib.BIN_DIV, B(lib.BIN_MUL, scale, m3),
+               B(lib.BIN_MUL, m2, M(lib.MAP_SQRT, m2, 0.0)))
+        # constant group (min == max): exactly 0.0, whatever residue m2 holds
+        const = lib.compare_scalar(lib.CMP_EQ, B(lib.BIN_SUB, mx, mn), 0.0)
+        notna = lib.compare_scalar(lib.CMP_NOTNA, sk, 0.0)
+        sk = M(lib.MAP_FILLNA,
+               lib.fixup_empty(sk, M(lib.MAP_RSUB, const, 1)), 0.0)
+        # n < 3 (all-NaN groups included) -> NaN; a NaN the formula itself
+        # produced for a non-constant group (inf values) stays NaN
+        ok = B(lib.BIN_MUL, lib.compare_scalar(lib.CMP_GE, cnt, 3.0),
+               B(lib.BIN_MAX, const, notna))
+        return lib.fixup_empty(sk, ok)
+
+    def groupby_anyall(self, by, all_: bool,
+                       dropna: bool = True) -> "HipDataframe":
+        """groupby any/all (GroupbyReduceImpl's any/all entries,
+        storage_formats/pandas/groupby.py:237-248): the truth test x != 0
+        as f64 with NaN kept rides the existing MAX (any) / MIN (all)
+        tables.  pandas skips NaN, so an all-NaN group is any=False /
+        all=True: the reduce leaves NaN there (the −inf/+inf identity fixed
+        up), and `NaN > 0` is False while `NaN != 0` is True.  int64 0/1
+        under dtype bool (the bool carrier)."""
+        self._single_rank_only("groupby all" if all_ else "groupby any")
+        bys = list(by) if isinstance(by, (list, tuple)) else [by]
+        val_names = [c for c in self.columns if c not in bys]
+        blk_cats = (self._partitions[0].block().cats
+                    if self._partitions else {})
+        dtc = self._dt_cols()
+        bad = [v for v in val_names if v in blk_cats or v in dtc]
+        if bad:
+            raise lib.HfError(
+                f"groupby any/all over string/datetime column(s) {bad}")
+
+        def truth(block: DeviceBlock) -> DeviceBlock:
+            cols = dict(block.columns)
+            for v in val_names:
+                x = block.columns[v]
+                t = lib.cast_f64(lib.compare_scalar(lib.CMP_NE, x, 0.0))
+                if x.dtype_code == lib.HF_FLOAT64:
+                    t = lib.fixup_empty(
+                        t, lib.compare_scalar(lib.CMP_NOTNA, x, 0.0))
+                cols[v] = t
+            return DeviceBlock(cols, block.length, block.cats)
+
+        dts = dict(self.dtypes)
+        for v in val_names:
+            dts[v] = np.dtype(np.float64)
+        tf = HipDataframe(
+            self._partition_mgr_cls.map_partitions(self._partitions, truth),
+            self._index, self.columns, self._row_lengths, pandas.Series(dts))
+        res = tf.groupby_reduce(by, "min" if all_ else "max", dropna=dropna)
+        block = res._partitions[0].block()
+        op = lib.CMP_NE if all_ else lib.CMP_GT
+        cols = {v: lib.compare_scalar(op, block.columns[v], 0.0)
+                for v in val_names}
+        part = HipDataframePartition(DeviceBlock(cols, block.length))
+        res2 = HipDataframe(
+            [part], res._index, val_names, list(res._row_lengths),
+            pandas.Series({v: np.dtype(bool) for v in val_names}))
+        return res2
+
+    def _central_moment_sums(self):
+        """Per column: (n, [Σd, Σd², Σd³, Σd⁴, min, max]) with d = x − mean,
+        pass 1 from the reduce partials, pass 2 one hf_group_moments call
+        per partition with a null gid (every row is group 0)."""
+        self._single_rank_only("skew/kurt")
+        p1 = self.tree_reduce(self.columns)
+        out = {}
+        for name in self.columns:
+            n = p1[name]["count"]
+            if n == 0:
+                out[name] = (0, None)
+                continue
+            centre = lib.put(np.array([p1[name]["sum"] / n],
+                                      dtype=np.float64))
+            table = lib.group_moments_table(1)
+            for p in self._partitions:
+                col = p.block().columns[name]
+                if col.length:
+                    lib.group_moments(None, lib.cast_f64(col), centre, 1,
+                                      table)
+            out[name] = (n, [float(x) for x in lib.get(table)])
+        return out
+
+    def skew_columns(self):
+        """Per-column unbiased skew (NaN skipped; pandas nanskew): the
+        corrected centred moments of groupby_skew, finished on host."""
+        res = {}
+        for name, (n, t) in self._central_moment_sums().items():
+            if n < 3:
+                res[name] = float("nan")
+            elif t[lib.GM_MIN] == t[lib.GM_MAX]:
+                res[name] = 0.0
+            else:
+                s1, s2, s3 = t[0], t[1], t[2]
+                e = s1 / n
+                m2 = s2 - n * e * e
+                m3 = s3 - 3.0 * e * s2 + 2.0 * n * e ** 3
+                res[name] = (n * np.sqrt(n - 1.0) / (n - 2.0)
+                             * m3 / (m2 * np.sqrt(m2)))
+        return res
+
+    def kurt_columns(self):
+        """Per-column unbiased excess kurtosis (NaN skipped; pandas
+        nankurt), m4 = Σd⁴ − 4eΣd³ + 6e²Σd² − 3n e⁴."""
+        res = {}
+        for name, (n, t) in self._central_moment_sums().items():
+            if n < 4:
+                res[name] = float("nan")
+            elif t[lib.GM_MIN] == t[lib.GM_MAX]:
+                res[name] = 0.0
+            else:
+                s1, s2, s3, s4 = t[0], t[1], t[2], t[3]
+                e = s1 / n
+                m2 = s2 - n * e * e
+                m4 = (s4 - 4.0 * e * s3 + 6.0 * e * e * s2
+                      - 3.0 * n * e ** 4)
+                d = (n - 2.0) * (n - 3.0)
+                res[name] = (n * (n + 1.0) * (n - 1.0) * m4 / (d * m2 * m2)
+                             - 3.0 * (n - 1.0) ** 2 / d)
+        return res
+
     def groupby_size(self, by) -> "HipDataframe":
         """groupby().size(): group row counts INCLUDING NaN values (and
         NaN keys dropped) — a ones column through the sum path."""

@@ -106,6 +106,9 @@ def load() -> ct.CDLL:
                                             ct.c_int, ct.c_int, ct.c_int64,
                                             ct.c_int64, ct.c_size_t,
                                             ct.c_size_t, ct.c_size_t]),
+            "hf_group_moments": (ct.c_int, [ct.c_void_p, ct.c_void_p,
+                                            ct.c_size_t, ct.c_int64,
+                                            ct.c_size_t]),
             "hf_fill_f64": (ct.c_int, [ct.c_size_t, ct.c_double, ct.c_int64]),
             "hf_fill_i64": (ct.c_int, [ct.c_size_t, ct.c_int64, ct.c_int64]),
             "hf_fill_randint": (ct.c_int, [ct.c_void_p, ct.c_uint64,
@@ -206,7 +209,8 @@ def exported_symbols():
         "hf_put", "hf_get", "hf_col_alloc", "hf_col_free", "hf_col_len",
         "hf_col_dtype", "hf_col_dptr", "hf_alloc_raw", "hf_free_raw",
         "hf_memset_raw", "hf_map_scalar", "hf_map_scalar_i64", "hf_binary",
-        "hf_reduce", "hf_groupby_accum", "hf_groupby_compact", "hf_fill_f64",
+        "hf_reduce", "hf_groupby_accum", "hf_group_moments",
+        "hf_groupby_compact", "hf_fill_f64",
         "hf_fixup_empty", "hf_sort_perm", "hf_fill_i64",
         "hf_fill_randint", "hf_fill_randf64", "hf_fill_randcdf",
         "hf_groupby_hash_accum", "hf_groupby_hash_compact",
@@ -411,6 +415,40 @@ def groupby_accum(keys: ColumnRef, vals: list, agg_op: int, key_min: int,
     _check(load().hf_groupby_accum(keys.handle, arr, len(vals), agg_op,
                                    key_min, n_slots, sums, rowcnt, counts),
            "hf_groupby_accum")
+
+
+# hf_group_moments table rows and its LDS/global path switch (hipframe.hip
+# GM_LDS_MAX): n_groups <= GM_LDS_MAX aggregates in block-private LDS tables
+GM_S1, GM_S2, GM_S3, GM_S4, GM_MIN, GM_MAX = range(6)
+GM_ROWS = 6
+GM_LDS_MAX = 1024
+
+
+def group_moments_table(n_groups: int) -> ColumnRef:
+    """A fresh hf_group_moments table: one float64 column of 6*n_groups
+    holding the rows Σd, Σd², Σd³, Σd⁴ (zeros), min (+inf), max (−inf)."""
+    tab = alloc(GM_ROWS * n_groups, HF_FLOAT64)
+    base = tab.dptr()
+    fill_f64(base, 0.0, 4 * n_groups)
+    fill_f64(base + 8 * GM_MIN * n_groups, float("inf"), n_groups)
+    fill_f64(base + 8 * GM_MAX * n_groups, float("-inf"), n_groups)
+    return tab
+
+
+def group_moments(gid, val: ColumnRef, centre: ColumnRef, n_groups: int,
+                  table: ColumnRef) -> None:
+    """Accumulate powers of d = val − centre[gid] and min/max of val into
+    `table` (group_moments_table layout).  gid None = every row is group 0;
+    negative gid and NaN val rows are skipped; gid >= n_groups raises."""
+    ensure_ready()
+    if centre.length != n_groups or table.length != GM_ROWS * n_groups \
+            or centre.dtype_code != HF_FLOAT64 \
+            or table.dtype_code != HF_FLOAT64:
+        raise HfError("group_moments: centre/table must be float64 columns "
+                      "of n_groups / 6*n_groups")
+    _check(load().hf_group_moments(gid.handle if gid is not None else None,
+                                   val.handle, centre.dptr(), n_groups,
+                                   table.dptr()), "hf_group_moments")
 
 
 def fill_f64(dptr: int, value: float, n: int) -> None:

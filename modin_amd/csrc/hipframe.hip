@@ -115,6 +115,7 @@ constexpr int64_t SCRATCH_NGROUPS = 136;
 constexpr int64_t SCRATCH_JOIN_HIST_ERR = 144;
 constexpr int64_t SCRATCH_JOIN_FIXUP_ERR = 152;
 constexpr int64_t SCRATCH_HASH_FULL = 160;
+constexpr int64_t SCRATCH_GM_ERR = 168;
 
 int set_err(int code, const char* where, const char* what) {
   g_err = std::string(where) + ": " + what;
@@ -1243,6 +1244,168 @@ __global__ void __launch_bounds__(512) k_gb_dense(
     if (HAVE_VAL) glob_slot_agg<AOP>(&gsums[s], lsums[s]);
     if (ROWCNT) atomicAdd(&growcnt[s], 1ULL);
     if (CNT) atomicAdd(&gcounts[s], (unsigned long long)lcnt[s]);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Fused group moments (hf_group_moments): Σd, Σd², Σd³, Σd⁴, min x, max x per
+// group with d = x − centre[group] — the centred second pass behind groupby
+// skew and frame skew/kurt (storage_formats/pandas/groupby.py:116 sums raw
+// powers; centring first keeps the moments conditioned at large mean/std).
+// Table rows are [6][n_groups] in LDS and in global memory alike.
+// ---------------------------------------------------------------------------
+
+constexpr int GM_ROWS = 6;
+constexpr int64_t GM_LDS_MAX = 1024;  // 7 x 8 B x 1024 = 56 KB: 2 blocks / CU
+
+template <bool LDS>
+__device__ __forceinline__ void gm_update(double* tab, int64_t ng, int64_t g,
+                                          double x, double c) {
+  const double d = x - c, d2 = d * d;
+  if (LDS) {
+    lds_slot_agg<HF_AGG_SUM>(&tab[g], d);
+    lds_slot_agg<HF_AGG_SUM>(&tab[ng + g], d2);
+    lds_slot_agg<HF_AGG_SUM>(&tab[2 * ng + g], d2 * d);
+    lds_slot_agg<HF_AGG_SUM>(&tab[3 * ng + g], d2 * d2);
+    lds_slot_agg<HF_AGG_MIN>(&tab[4 * ng + g], x);
+    lds_slot_agg<HF_AGG_MAX>(&tab[5 * ng + g], x);
+  } else {
+    glob_slot_agg<HF_AGG_SUM>(&tab[g], d);
+    glob_slot_agg<HF_AGG_SUM>(&tab[ng + g], d2);
+    glob_slot_agg<HF_AGG_SUM>(&tab[2 * ng + g], d2 * d);
+    glob_slot_agg<HF_AGG_SUM>(&tab[3 * ng + g], d2 * d2);
+    glob_slot_agg<HF_AGG_MIN>(&tab[4 * ng + g], x);
+    glob_slot_agg<HF_AGG_MAX>(&tab[5 * ng + g], x);
+  }
+}
+
+// LDS path: block-private copy of the six rows + centre, touched slots only
+// are flushed.  gid < 0 rows are skipped, gid >= n_groups rows are counted.
+__global__ void __launch_bounds__(512) k_gm_lds(
+    const int64_t* __restrict__ gid, const double* __restrict__ val, int64_t n,
+    const double* __restrict__ centre, int64_t ng, double* __restrict__ gtab,
+    unsigned long long* __restrict__ err) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  double* ltab = reinterpret_cast<double*>(smem_raw);       // [6][ng]
+  double* lc = ltab + GM_ROWS * ng;                         // [ng]
+  unsigned char* ltouch = reinterpret_cast<unsigned char*>(lc + ng);
+  for (int64_t s = threadIdx.x; s < ng; s += blockDim.x) {
+    ltab[s] = ltab[ng + s] = ltab[2 * ng + s] = ltab[3 * ng + s] = 0.0;
+    ltab[4 * ng + s] = agg_identity<HF_AGG_MIN>();
+    ltab[5 * ng + s] = agg_identity<HF_AGG_MAX>();
+    lc[s] = centre[s];
+    ltouch[s] = 0;
+  }
+  __syncthreads();
+  auto row = [&](int64_t g, double x) {
+    if (g < 0) return;
+    if (g >= ng) { atomicAdd(err, 1ULL); return; }
+    if (x != x) return;
+    ltouch[g] = 1;
+    gm_update<true>(ltab, ng, g, x, lc[g]);
+  };
+  const int64_t npair = n >> 1;
+  const longlong2* gid2 = reinterpret_cast<const longlong2*>(gid);
+  const double2* val2 = reinterpret_cast<const double2*>(val);
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (; i < npair; i += stride) {
+    const longlong2 gg = gid2[i];
+    const double2 v = val2[i];
+    row(gg.x, v.x);
+    row(gg.y, v.y);
+  }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) row(gid[n - 1], val[n - 1]);
+  __syncthreads();
+  for (int64_t s = threadIdx.x; s < ng; s += blockDim.x) {
+    if (!ltouch[s]) continue;
+    glob_slot_agg<HF_AGG_SUM>(&gtab[s], ltab[s]);
+    glob_slot_agg<HF_AGG_SUM>(&gtab[ng + s], ltab[ng + s]);
+    glob_slot_agg<HF_AGG_SUM>(&gtab[2 * ng + s], ltab[2 * ng + s]);
+    glob_slot_agg<HF_AGG_SUM>(&gtab[3 * ng + s], ltab[3 * ng + s]);
+    glob_slot_agg<HF_AGG_MIN>(&gtab[4 * ng + s], ltab[4 * ng + s]);
+    glob_slot_agg<HF_AGG_MAX>(&gtab[5 * ng + s], ltab[5 * ng + s]);
+  }
+}
+
+// Global path: the same arithmetic with agent-scope atomics straight into
+// the table; centre is read through the cache.
+__global__ void __launch_bounds__(BLOCK) k_gm_global(
+    const int64_t* __restrict__ gid, const double* __restrict__ val, int64_t n,
+    const double* __restrict__ centre, int64_t ng, double* __restrict__ gtab,
+    unsigned long long* __restrict__ err) {
+  auto row = [&](int64_t g, double x) {
+    if (g < 0) return;
+    if (g >= ng) { atomicAdd(err, 1ULL); return; }
+    if (x != x) return;
+    gm_update<false>(gtab, ng, g, x, centre[g]);
+  };
+  const int64_t npair = n >> 1;
+  const longlong2* gid2 = reinterpret_cast<const longlong2*>(gid);
+  const double2* val2 = reinterpret_cast<const double2*>(val);
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (; i < npair; i += stride) {
+    const longlong2 gg = gid2[i];
+    const double2 v = val2[i];
+    row(gg.x, v.x);
+    row(gg.y, v.y);
+  }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) row(gid[n - 1], val[n - 1]);
+}
+
+// Null-gid form (every row is group 0: frame skew/kurt): register partials,
+// wave shuffle + block combine, six atomics per block.
+__global__ void __launch_bounds__(BLOCK) k_gm_one(
+    const double* __restrict__ val, int64_t n,
+    const double* __restrict__ centre, double* __restrict__ gtab) {
+  const double c = centre[0];
+  double s1 = 0.0, s2 = 0.0, s3 = 0.0, s4 = 0.0;
+  double mn = agg_identity<HF_AGG_MIN>(), mx = agg_identity<HF_AGG_MAX>();
+  auto row = [&](double x) {
+    if (x != x) return;
+    const double d = x - c, d2 = d * d;
+    s1 += d; s2 += d2; s3 += d2 * d; s4 += d2 * d2;
+    mn = fmin(mn, x); mx = fmax(mx, x);
+  };
+  const int64_t npair = n >> 1;
+  const double2* val2 = reinterpret_cast<const double2*>(val);
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (; i < npair; i += stride) {
+    const double2 v = val2[i];
+    row(v.x);
+    row(v.y);
+  }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) row(val[n - 1]);
+  for (int off = 32; off > 0; off >>= 1) {
+    s1 += __shfl_down(s1, off);
+    s2 += __shfl_down(s2, off);
+    s3 += __shfl_down(s3, off);
+    s4 += __shfl_down(s4, off);
+    mn = fmin(mn, __shfl_down(mn, off));
+    mx = fmax(mx, __shfl_down(mx, off));
+  }
+  __shared__ double part[BLOCK / 64][GM_ROWS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+    part[wave][0] = s1; part[wave][1] = s2; part[wave][2] = s3;
+    part[wave][3] = s4; part[wave][4] = mn; part[wave][5] = mx;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < BLOCK / 64; ++w) {
+      s1 += part[w][0]; s2 += part[w][1]; s3 += part[w][2]; s4 += part[w][3];
+      mn = fmin(mn, part[w][4]); mx = fmax(mx, part[w][5]);
+    }
+    if (mn <= mx) {  // the block saw at least one non-NaN row
+      glob_slot_agg<HF_AGG_SUM>(&gtab[0], s1);
+      glob_slot_agg<HF_AGG_SUM>(&gtab[1], s2);
+      glob_slot_agg<HF_AGG_SUM>(&gtab[2], s3);
+      glob_slot_agg<HF_AGG_SUM>(&gtab[3], s4);
+      glob_slot_agg<HF_AGG_MIN>(&gtab[4], mn);
+      glob_slot_agg<HF_AGG_MAX>(&gtab[5], mx);
+    }
   }
 }
 
@@ -3440,6 +3603,65 @@ int hf_groupby_accum(const hf_col* keys, const hf_col* const* vals, int nvals,
                           std::integral_constant<bool, false>{});
   }
   return set_err(HF_ERR_ARG, "hf_groupby_accum", "nvals out of range");
+}
+
+int hf_group_moments(const hf_col* gid, const hf_col* val, uintptr_t centre,
+                     int64_t n_groups, uintptr_t table) {
+  HF_NEED_INIT("hf_group_moments");
+  if (!val || val->dtype != HF_FLOAT64 || !centre || !table)
+    return set_err(HF_ERR_ARG, "hf_group_moments",
+                   "val must be float64; centre/table must be non-null");
+  if (n_groups <= 0)
+    return set_err(HF_ERR_ARG, "hf_group_moments", "n_groups<=0");
+  if (gid && (gid->dtype != HF_INT64 || gid->len != val->len))
+    return set_err(HF_ERR_ARG, "hf_group_moments",
+                   "gid must be an int64 column of val's length");
+  if (!gid && n_groups != 1)
+    return set_err(HF_ERR_ARG, "hf_group_moments",
+                   "a null gid means one group (n_groups must be 1)");
+  const int64_t n = val->len;
+  if (n == 0) return HF_OK;
+  const double* d_val = (const double*)val->dptr;
+  const double* d_c = (const double*)centre;
+  double* d_tab = (double*)table;
+  if (!gid) {
+    int64_t grid = grid_for((n >> 1) + 1);
+    if (grid > 1024) grid = 1024;  // six same-address atomics per block
+    return timed_launch("gm_one", [&] {
+      hipLaunchKernelGGL(k_gm_one, dim3((uint32_t)grid), dim3(BLOCK), 0,
+                         g.stream, d_val, n, d_c, d_tab);
+    });
+  }
+  unsigned long long* d_err =
+      (unsigned long long*)((char*)g.d_scratch + SCRATCH_GM_ERR);
+  HF_HIP("hf_group_moments", hipMemsetAsync(d_err, 0, 8, g.stream));
+  const int64_t* d_gid = (const int64_t*)gid->dptr;
+  int rc;
+  if (n_groups <= GM_LDS_MAX) {
+    int64_t grid = n / 65536 + 1;
+    if (grid > 512) grid = 512;
+    const uint32_t lds = (uint32_t)(n_groups * ((GM_ROWS + 1) * 8 + 1));
+    rc = timed_launch("gm_lds", [&] {
+      hipLaunchKernelGGL(k_gm_lds, dim3((uint32_t)grid), dim3(512), lds,
+                         g.stream, d_gid, d_val, n, d_c, n_groups, d_tab,
+                         d_err);
+    });
+  } else {
+    rc = timed_launch("gm_global", [&] {
+      hipLaunchKernelGGL(k_gm_global, dim3((uint32_t)grid_for((n >> 1) + 1)),
+                         dim3(BLOCK), 0, g.stream, d_gid, d_val, n, d_c,
+                         n_groups, d_tab, d_err);
+    });
+  }
+  if (rc != HF_OK) return rc;
+  unsigned long long h_err = 0;
+  HF_HIP("hf_group_moments",
+         hipMemcpyAsync(&h_err, d_err, 8, hipMemcpyDeviceToHost, g.stream));
+  HF_HIP("hf_group_moments", hipStreamSynchronize(g.stream));
+  if (h_err)
+    return set_err(HF_ERR_ARG, "hf_group_moments",
+                   "gid >= n_groups (rows were not accumulated)");
+  return HF_OK;
 }
 
 int hf_groupby_compact(uintptr_t sums, uintptr_t rowcnt, uintptr_t counts,

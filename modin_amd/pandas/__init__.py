@@ -332,6 +332,31 @@ class _HipPandasBase:
     def var(self, ddof: int = 1):
         return self._lower(self._query_compiler.var(ddof=ddof))
 
+    def _shape_stat(self, name, axis=0, skipna=True, numeric_only=False):
+        if axis in (1, "columns"):
+            raise lib.HfError(f"{name}(axis=1) is not supported")
+        if not skipna:
+            raise lib.HfError(f"{name}(skipna=False) is not supported")
+        qc = self._query_compiler
+        if numeric_only:
+            keep = [c for c in qc.columns
+                    if isinstance(qc.dtypes[c], np.dtype)
+                    and qc.dtypes[c] in (np.dtype(np.int64),
+                                         np.dtype(np.float64))]
+            qc = qc.getitem_column_array(keep)
+        return self._lower(getattr(qc, name)())
+
+    def skew(self, axis=0, skipna: bool = True, numeric_only: bool = False):
+        """pandas skew: unbiased sample skewness per column, NaN skipped
+        (two passes on the fused centred-moments kernel)."""
+        return self._shape_stat("skew", axis, skipna, numeric_only)
+
+    def kurt(self, axis=0, skipna: bool = True, numeric_only: bool = False):
+        """pandas kurt: unbiased excess kurtosis per column, NaN skipped."""
+        return self._shape_stat("kurt", axis, skipna, numeric_only)
+
+    kurtosis = kurt
+
     def sem(self, ddof: int = 1):
         """pandas sem: std/sqrt(count), composed from the one-pass
         reduce partials."""
@@ -1770,7 +1795,12 @@ class DataFrameGroupBy:
         if not self._as_index:
             # reference reduce fix-up (algebra/groupby.py:278): keys become
             # leading columns over a fresh RangeIndex
-            return from_pandas(out.to_pandas().reset_index())
+            pdf = out.to_pandas().reset_index()
+            bools = [c for c in pdf.columns if pdf[c].dtype == bool]
+            res = from_pandas(pdf.astype({c: np.int64 for c in bools}))
+            for c in bools:  # any/all: int64 0/1 under dtype bool
+                res._query_compiler._modin_frame.dtypes[c] = np.dtype(bool)
+            return res
         return out
 
     def sum(self):
@@ -1804,6 +1834,15 @@ class DataFrameGroupBy:
 
     def median(self):
         return self._agg("median")
+
+    def skew(self):
+        return self._agg("skew")
+
+    def any(self):  # noqa: A003
+        return self._agg("any")
+
+    def all(self):  # noqa: A003
+        return self._agg("all")
 
     def sem(self, ddof: int = 1):
         """pandas DataFrameGroupBy.sem: std/sqrt(count) from the
@@ -1957,7 +1996,7 @@ class DataFrameGroupBy:
         return out["size"].rename(None)
 
     _AGGS = ("sum", "count", "mean", "min", "max", "var", "std",
-             "median", "first", "last", "prod")
+             "median", "first", "last", "prod", "skew", "any", "all")
 
     def agg(self, how=None, **named):
         """str, list-of-str (MultiIndex columns, pandas col-major order),

@@ -217,8 +217,35 @@ class HipQueryCompiler:
         return self._tag_key_index(self.__constructor__(
             self._modin_frame.groupby_var(by, ddof, sqrt=True)), by)
 
+    # skew/any/all: the last three GroupbyReduceImpl entries
+    # (storage_formats/pandas/groupby.py:237-248)
+    _groupby_skew = GroupByReduce.register("skew")
+    _groupby_any = GroupByReduce.register("any")
+    _groupby_all = GroupByReduce.register("all")
+
+    def groupby_skew(self, by) -> "HipQueryCompiler":
+        return self._tag_key_index(type(self)._groupby_skew(self, by), by)
+
+    def groupby_any(self, by, dropna: bool = True) -> "HipQueryCompiler":
+        return self._tag_key_index(
+            type(self)._groupby_any(self, by, dropna=dropna), by)
+
+    def groupby_all(self, by, dropna: bool = True) -> "HipQueryCompiler":
+        return self._tag_key_index(
+            type(self)._groupby_all(self, by, dropna=dropna), by)
+
     def median(self):
         vals = self._modin_frame.median_columns()
+        return pandas.Series(vals, dtype=np.float64)
+
+    def skew(self):
+        """Column skew (reference binds it as Reduce, query_compiler.py:1144)."""
+        vals = self._modin_frame.skew_columns()
+        return pandas.Series(vals, dtype=np.float64)
+
+    def kurt(self):
+        """Column excess kurtosis (reference Reduce, query_compiler.py:1148)."""
+        vals = self._modin_frame.kurt_columns()
         return pandas.Series(vals, dtype=np.float64)
 
     def clip(self, lower=None, upper=None) -> "HipQueryCompiler":
@@ -828,18 +855,23 @@ class HipQueryCompiler:
             "prod": type(self).groupby_prod,
             "first": type(self).groupby_first,
             "last": type(self).groupby_last,
+            "skew": type(self).groupby_skew,
+            "any": type(self).groupby_any,
+            "all": type(self).groupby_all,
         }.get(agg)
         if fn is None:
             raise lib.HfError(
                 f"groupby agg {agg!r} not implemented on the HipNative backend"
             )
-        if agg in ("sum", "count", "mean", "min", "max"):
+        if agg in ("sum", "count", "mean", "min", "max", "any", "all"):
+            # these ride groupby_reduce, which handles dropna itself
             return self._tag_key_index(fn(self, by, dropna=dropna), by)
         if not dropna:
             name = {"var": "groupby_var", "std": "groupby_std",
                     "median": "groupby_median", "first": "groupby_first",
                     "last": "groupby_last",
-                    "prod": "groupby_prod"}[agg]
+                    "prod": "groupby_prod",
+                    "skew": "groupby_skew"}[agg]
             return self._tag_key_index(
                 self.groupby_tail_agg(by, name, dropna=False), by)
         return self._tag_key_index(fn(self, by), by)
