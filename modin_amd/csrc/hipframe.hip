@@ -22,9 +22,11 @@
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
+#include <memory>
 #include <string>
 #include <type_traits>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "../../include/hipframe.h"
@@ -33,27 +35,27 @@
 // module state & error plumbing
 // ---------------------------------------------------------------------------
 
-struct hf_col {
-  void*   dptr;
-  int64_t len;
-  int     dtype;
-  int     gpu;
-  // cached per-bucket histogram for the radix groupby path (device u64
-  // array of n_buckets entries).  Valid when hist_kmin/hist_nb match the
-  // current query.  The column is immutable, so this is the device analog
-  // of the reference's lazy-metadata caches (modin/core/dataframe/pandas/
-  // metadata/) — a repeated groupby on the same key column skips the
-  // histogram pass.
-  void*   d_hist = nullptr;
+// Everything the radix groupby path caches on a key column.  Derivation
+// chain: histogram -> layout (cursor-init + work items) -> scatter plan;
+// d_k32 hangs off key_min alone.  The member functions at the end are the
+// only places that list the fields to free.
+struct GbKeyCache {
+  // cached per-bucket histogram for the radix groupby path (host copy, one
+  // entry per bucket; empty = none).  Valid when hist_kmin/hist_nb/
+  // hist_nslots match the current query.  The column is immutable, so this
+  // is the device analog of the reference's lazy-metadata caches
+  // (modin/core/dataframe/pandas/metadata/) — a repeated groupby on the same
+  // key column skips the histogram pass.
+  std::vector<int64_t> hist;
   int64_t hist_kmin = 0;
   int64_t hist_nb = 0;
   int64_t hist_nslots = 0;       // exact n_slots the histogram was cut for
   // cached u32 shifted copy of an int64 key column (key - key_min), the
   // narrow-key fast path for the radix scatter (12 B/row instead of 16).
-  // Same immutable-column caching rationale as d_hist.
+  // Same immutable-column caching rationale as hist.
   void*   d_k32 = nullptr;
   int64_t k32_min = 0;
-  // cached radix-scatter layout derived from d_hist: device cursor-init
+  // cached radix-scatter layout derived from hist: device cursor-init
   // array (region starts) + device work items — steady-state groupby
   // launches copy cursors D2D and never touch the host (no H2D, no sync)
   void*   d_curinit = nullptr;   // u32[nb]
@@ -66,7 +68,7 @@ struct hf_col {
   // and later calls replay a pure value permutation that never reads keys
   // (k_gb_replay).  One plan per column, valid for exactly
   // (plan_kmin, plan_nslots, plan_rl) at GB_PLAN_TILE rows per tile; another
-  // geometry re-records.  Invalidated with d_hist (same derivation chain).
+  // geometry re-records.  Invalidated with hist (same derivation chain).
   void*   d_plan_dst = nullptr;  // u16[n]: row -> slot in its tile's bucket-
                                  // sorted LDS staging; 0xFFFF = key out of range
   void*   d_plan_rk = nullptr;   // u16[radix_rows]: low-key stream P2 reads
@@ -77,6 +79,18 @@ struct hf_col {
   int64_t plan_kmin = 0;
   int64_t plan_nslots = 0;
   int     plan_rl = 0;           // 0 = no plan
+
+  void drop_plan();     // free the plan buffers, plan_rl = 0
+  void drop_derived();  // the histogram changed: drop the layout and the plan
+  void release();       // the column dies: give every device block back
+};
+
+struct hf_col {
+  void*   dptr;
+  int64_t len;
+  int     dtype;
+  int     gpu;
+  GbKeyCache gb;
 };
 
 namespace {
@@ -89,12 +103,6 @@ struct State {
   bool        inited = false;
   int         gpu = -1;
   hipStream_t stream = nullptr;
-  // consumer stream for the overlapped radix-groupby P2 (all OTHER compute
-  // stays on `stream`; stream2 work is always fenced back onto `stream`
-  // with an event before any buffer it read is freed, so the allocator's
-  // single-stream reuse argument still holds)
-  hipStream_t stream2 = nullptr;
-  hipEvent_t  ov_ev[10] = {};
   // small persistent device scratch: reduce accumulators + error word +
   // compact bookkeeping
   void*       d_scratch = nullptr;   // see layout below
@@ -160,10 +168,9 @@ int resolve_stats(const char* where) {
   return HF_OK;
 }
 
-// launch helper with optional event bracketing; pass the stream the launch
-// targets (default: the module stream)
+// launch helper with optional event bracketing on the module stream
 template <typename F>
-int timed_launch_on(const char* name, hipStream_t s, F&& launch) {
+int timed_launch(const char* name, F&& launch) {
   if (!g.profiling) {
     launch();
     hipError_t e = hipGetLastError();
@@ -174,19 +181,37 @@ int timed_launch_on(const char* name, hipStream_t s, F&& launch) {
   p.name = name;
   HF_HIP(name, hipEventCreate(&p.a));
   HF_HIP(name, hipEventCreate(&p.b));
-  HF_HIP(name, hipEventRecord(p.a, s));
+  HF_HIP(name, hipEventRecord(p.a, g.stream));
   launch();
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_hip_err(name, e);
-  HF_HIP(name, hipEventRecord(p.b, s));
+  HF_HIP(name, hipEventRecord(p.b, g.stream));
   g.pending.push_back(p);
   if (g.pending.size() > 4096) return resolve_stats(name);
   return HF_OK;
 }
 
+// Runtime value -> compile-time tag for a generic lambda: f receives a
+// std::integral_constant and the caller reads decltype(tag)::value.  Callers
+// validate agg_op / nvals first.  Only the combinations a caller actually
+// nests are instantiated.
 template <typename F>
-int timed_launch(const char* name, F&& launch) {
-  return timed_launch_on(name, g.stream, std::forward<F>(launch));
+int with_bool(bool b, F&& f) {
+  return b ? f(std::true_type{}) : f(std::false_type{});
+}
+template <typename F>
+int with_aop(int agg_op, F&& f) {
+  return agg_op == HF_AGG_SUM   ? f(std::integral_constant<int, HF_AGG_SUM>{})
+         : agg_op == HF_AGG_MIN ? f(std::integral_constant<int, HF_AGG_MIN>{})
+                                : f(std::integral_constant<int, HF_AGG_MAX>{});
+}
+template <int MAX, int N = 0, typename F>
+int with_nvals(int nv, F&& f) {  // nv in [0, MAX]
+  if (nv == N) return f(std::integral_constant<int, N>{});
+  if constexpr (N < MAX)
+    return with_nvals<MAX, N + 1>(nv, std::forward<F>(f));
+  else
+    return set_err(HF_ERR_ARG, "groupby", "nvals out of range");
 }
 
 constexpr int BLOCK = 256;
@@ -267,17 +292,57 @@ inline hipError_t dev_free(void* p, hipStream_t s) {
   return hipSuccess;
 }
 
-// drop a key column's cached scatter plan (see hf_col)
-void plan_free(hf_col* c) {
-  void** bufs[4] = {&c->d_plan_dst, &c->d_plan_rk, &c->d_plan_tab,
-                    &c->d_plan_meta};
-  for (void** b : bufs) {
-    if (*b) dev_free(*b, g.stream);
-    *b = nullptr;
+// Scoped device block on the module stream: goes back to the allocator on
+// scope exit (so every early return is leak-free) unless release() hands it
+// to a longer-lived owner.  Move-only.
+class DevBuf {
+ public:
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p_(o.release()) {}
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { if (p_) (void)dev_free(p_, g.stream); }
+  hipError_t alloc(int64_t bytes) {  // call once per holder
+    hipError_t e = dev_alloc(&p_, bytes, g.stream);
+    if (e != hipSuccess) p_ = nullptr;
+    return e;
   }
-  c->plan_rl = 0;
+  void* release() { void* p = p_; p_ = nullptr; return p; }
+  template <typename T>
+  T* as() const { return static_cast<T*>(p_); }
+
+ private:
+  void* p_ = nullptr;
+};
+
+// give a cached device block back and forget it (a column freed after
+// hf_shutdown only forgets: the stream and allocator are gone)
+void drop_dev(void*& p) {
+  if (p && g.inited) (void)dev_free(p, g.stream);
+  p = nullptr;
 }
 }  // namespace
+
+void GbKeyCache::drop_plan() {
+  drop_dev(d_plan_dst);
+  drop_dev(d_plan_rk);
+  drop_dev(d_plan_tab);
+  drop_dev(d_plan_meta);
+  plan_rl = 0;
+}
+
+void GbKeyCache::drop_derived() {
+  drop_dev(d_curinit);
+  drop_dev(d_work);
+  work_n = radix_rows = 0;
+  radix_rl = 0;
+  drop_plan();
+}
+
+void GbKeyCache::release() {
+  drop_derived();
+  drop_dev(d_k32);
+}
 
 // ---------------------------------------------------------------------------
 // kernels: Map (elementwise scalar) — algebra/map.py:28 device form
@@ -745,12 +810,6 @@ __global__ void __launch_bounds__(BLOCK) k_gb_hist(
     if (lhist[t]) atomicAdd(&hist[t], (unsigned long long)lhist[t]);
 }
 
-// P1: LDS-staged bucket-sorted tiles.  Row pairs load 16 B-vectorized
-// (longlong2/double2), are ranked into a per-tile LDS histogram (`ds_add`),
-// prefix-scanned wave-parallel, staged bucket-SORTED in LDS, and written out
-// coalesced — each tile emits one contiguous chunk per bucket stream
-// (probe: 2.6x the register-staged direct scatter).  RPT rows/thread
-// (even); NV value columns; odd tail row handled by block 0 up front.
 __global__ void __launch_bounds__(BLOCK) k_conv_keys32(
     const int64_t* __restrict__ keys, int64_t n, int64_t key_min,
     unsigned* __restrict__ out) {
@@ -762,55 +821,59 @@ __global__ void __launch_bounds__(BLOCK) k_conv_keys32(
   }
 }
 
-// Software-pipelined tile loop (round-2 probe winner, tools/ring_probe.hip:
-// P1 6.69 -> 5.52 ms on the 1e9-row north star).  Raw global loads for tile
-// t+1 are issued right after tile t's LDS staging — the registers are dead at
-// that point — so their ~700-cycle latency hides under t's writeout + barrier
-// instead of serializing at the top of the next iteration (the 81%
-// wave-parked stall of the round-1 kernel, profiles/r01b/sq_scatter.txt).
-// row0/row1 bound the input rows (the overlapped-P2 path scatters in
-// chunks; row0 is always even, only the LAST chunk may end odd)
-// REC: the plan-recording variant (first radix call on a key column).  Same
-// work, plus it keeps what a replay needs: each row's staging slot (`dst`,
-// one coalesced ushort2 per row pair), the tile's offset/base table row, the
-// tail row's region slot and the out-of-range count.
 struct GbPlanRec {
   unsigned short* dst;
   unsigned* tab;
   unsigned long long* meta;
 };
 
-template <int NV, int RPT, int BLK, int RL, bool K32, bool REC = false>
+// P1: LDS-staged bucket-sorted tiles.  Row pairs load 16 B-vectorized
+// (longlong2/double2), are ranked into a per-tile LDS histogram (`ds_add`),
+// prefix-scanned wave-parallel, staged bucket-SORTED in LDS, and written out
+// coalesced — each tile emits one contiguous chunk per bucket stream
+// (probe: 2.6x the register-staged direct scatter).  RPT rows/thread
+// (even); NV value columns; odd tail row handled by block 0 up front.
+// Software-pipelined tile loop (round-2 probe winner, tools/ring_probe.hip:
+// P1 6.69 -> 5.52 ms on the 1e9-row north star).  Raw global loads for tile
+// t+1 are issued right after tile t's LDS staging — the registers are dead at
+// that point — so their ~700-cycle latency hides under t's writeout + barrier
+// instead of serializing at the top of the next iteration (the 81%
+// wave-parked stall of the round-1 kernel, profiles/r01b/sq_scatter.txt).
+// REC: the plan-recording variant (first radix call on a key column).  Same
+// work, plus it keeps what a replay needs: each row's staging slot (`dst`,
+// one coalesced ushort2 per row pair), the tile's offset/base table row, the
+// tail row's region slot and the out-of-range count.  It reads the int64
+// keys; the plan-less variant (!REC) reads the cached u32 copy.
+template <int NV, int RPT, int BLK, int RL, bool REC>
 __global__ void __launch_bounds__(BLK) k_gb_scatter(
     const int64_t* __restrict__ keys, const unsigned* __restrict__ keys32,
     const double* __restrict__ v0,
-    const double* __restrict__ v1, int64_t row0, int64_t row1,
+    const double* __restrict__ v1, int64_t n,
     int64_t key_min, int64_t n_slots,
     int nb, unsigned* __restrict__ cursors,
     double* __restrict__ r0, double* __restrict__ r1,
     unsigned short* __restrict__ rk, unsigned long long* __restrict__ err,
     GbPlanRec rec) {
+  constexpr bool K32 = !REC;
   constexpr int TILE = BLK * RPT;
   constexpr int PAIRS = RPT / 2;
   static_assert(!REC || TILE < 0xFFFF, "plan dst is u16 with 0xFFFF reserved");
-  if ((row1 & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
     // odd tail row: direct single-row reservation + write
-    const int64_t k =
-        K32 ? (int64_t)keys32[row1 - 1] : keys[row1 - 1] - key_min;
+    const int64_t k = K32 ? (int64_t)keys32[n - 1] : keys[n - 1] - key_min;
     if ((uint64_t)k < (uint64_t)n_slots) {
       const int b = (int)(k >> RL);
       const int64_t pos = (int64_t)atomicAdd(&cursors[b], 1u);
       rk[pos] = (unsigned short)(k & ((1 << RL) - 1));
-      if (NV > 0) r0[pos] = v0[row1 - 1];
-      if (NV > 1) r1[pos] = v1[row1 - 1];
+      if (NV > 0) r0[pos] = v0[n - 1];
+      if (NV > 1) r1[pos] = v1[n - 1];
       if (REC) rec.meta[0] = (unsigned long long)pos;
     } else {
       atomicAdd(err, 1ULL);
       if (REC) atomicAdd(&rec.meta[1], 1ULL);
     }
   }
-  const int64_t pr0 = row0 >> 1;
-  const int64_t npair_total = ((row1 & ~1LL) - row0) >> 1;
+  const int64_t npair_total = n >> 1;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   double* sval0 = reinterpret_cast<double*>(smem_raw);            // [TILE]
   double* sval1 = sval0 + (NV > 1 ? TILE : 0);
@@ -836,13 +899,12 @@ __global__ void __launch_bounds__(BLK) k_gb_scatter(
     for (int j = 0; j < PAIRS; ++j) {
       const int64_t pj = tile * (TILE / 2) + (int64_t)j * BLK + threadIdx.x;
       if (pj < npair_total) {
-        const int64_t pr = pr0 + pj;
         if (K32)
-          kraw[j] = reinterpret_cast<const uint2*>(keys32)[pr];
+          kraw[j] = reinterpret_cast<const uint2*>(keys32)[pj];
         else
-          kraw64[j] = reinterpret_cast<const longlong2*>(keys)[pr];
-        if (NV > 0) vraw0[j] = reinterpret_cast<const double2*>(v0)[pr];
-        if (NV > 1) vraw1[j] = reinterpret_cast<const double2*>(v1)[pr];
+          kraw64[j] = reinterpret_cast<const longlong2*>(keys)[pj];
+        if (NV > 0) vraw0[j] = reinterpret_cast<const double2*>(v0)[pj];
+        if (NV > 1) vraw1[j] = reinterpret_cast<const double2*>(v1)[pj];
       }
     }
   };
@@ -916,7 +978,6 @@ __global__ void __launch_bounds__(BLK) k_gb_scatter(
       }
     }
     if (REC) {
-      // row0 == 0 on the plan path, so pair pj of the tile is input pair pj
 #pragma unroll
       for (int j = 0; j < PAIRS; ++j) {
         const int64_t pj = tile * (TILE / 2) + (int64_t)j * BLK + threadIdx.x;
@@ -927,7 +988,7 @@ __global__ void __launch_bounds__(BLK) k_gb_scatter(
           d.y = lb[bslot] >= 0
                     ? (unsigned short)(it_off[lb[bslot]] + lr[bslot])
                     : 0xFFFF;
-          reinterpret_cast<ushort2*>(rec.dst)[pr0 + pj] = d;
+          reinterpret_cast<ushort2*>(rec.dst)[pj] = d;
         }
       }
     }
@@ -1072,56 +1133,27 @@ __global__ void k_gb_plan_err(const unsigned long long* __restrict__ meta,
   if (blockIdx.x == 0 && threadIdx.x == 0 && meta[1]) atomicAdd(err, meta[1]);
 }
 
-// Build P2 work items ON DEVICE from cursor snapshots (the overlapped
-// path): split every bucket's fresh region slice [lo[b], hi[b]) into
-// <= max_len-row items.  One block; item order is irrelevant.
-__global__ void k_gb_make_work(const unsigned* __restrict__ lo,
-                               const unsigned* __restrict__ hi, int nb,
-                               int max_len, GbWorkItem* __restrict__ out,
-                               int* __restrict__ count) {
-  if (blockIdx.x != 0) return;
-  __shared__ int s_cnt;
-  if (threadIdx.x == 0) s_cnt = 0;
-  __syncthreads();
-  for (int b = threadIdx.x; b < nb; b += blockDim.x) {
-    int64_t s0 = lo[b];
-    const int64_t s1 = hi[b];
-    while (s0 < s1) {
-      const int len = (int)min((int64_t)max_len, s1 - s0);
-      const int i = atomicAdd(&s_cnt, 1);
-      out[i] = GbWorkItem{s0, b, len};
-      s0 += len;
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) *count = s_cnt;
-}
-
-// P2: one work item per (bucket, chunk); one value column per launch.
+// P2: one work item per (bucket, chunk), one block per item; one value
+// column per launch.
 // ROWCNT: also mark group presence (first column / keys-only pass).  The
 // global rowcnt table is PRESENCE-ONLY everywhere (compaction tests >0;
 // per-column counts live in the counts table), so the per-row mark is a
 // plain LDS byte store (last-writer-wins, LDS is CU-local) — no atomic.
 // CNT: also merge per-slot non-NaN counts for this column.
-// 2 rows/lane vectorized (regions are 64-row aligned; odd chunk tails are
-// only ever the last chunk of a bucket).
-// n_work (optional): device item count — the overlapped path launches an
-// upper-bound grid and builds the items on device from cursor snapshots
-// (k_gb_make_work), so extra blocks exit on the count.  Item starts may
-// have any parity there: scalar head/tail rows keep the 2-row vector
-// middle aligned.
+// 2 rows/lane vectorized.  INVARIANT: every item start is even — a start is
+// region base + k * AGG_CHUNK, regions are 64-row aligned and AGG_CHUNK is
+// even (ensure_radix_layout) — so the ushort2/double2 streams are aligned
+// from the first row; only the last chunk of a bucket can have an odd tail.
 template <bool ROWCNT, bool CNT, bool HAVE_VAL, int RL, int AOP>
 __global__ void __launch_bounds__(512) k_gb_bucket_agg(
     const double* __restrict__ vals, const unsigned short* __restrict__ lowkeys,
-    const GbWorkItem* __restrict__ work, const int* __restrict__ n_work,
-    int64_t n_slots,
+    const GbWorkItem* __restrict__ work, int64_t n_slots,
     double* __restrict__ gsums, unsigned long long* __restrict__ growcnt,
     unsigned long long* __restrict__ gcounts) {
   constexpr int RANGE = 1 << RL;
   __shared__ double lsums[HAVE_VAL ? RANGE : 1];
   __shared__ unsigned lcnt[CNT ? RANGE : 1];
   __shared__ unsigned char ltouch[RANGE];
-  if (n_work && blockIdx.x >= (unsigned)*n_work) return;
   const GbWorkItem w = work[blockIdx.x];
   for (int s = threadIdx.x; s < RANGE; s += blockDim.x) {
     if (HAVE_VAL) lsums[s] = agg_identity<AOP>();
@@ -1141,9 +1173,7 @@ __global__ void __launch_bounds__(512) k_gb_bucket_agg(
       }
     }
   };
-  int64_t a0 = w.start;
-  if ((a0 & 1) && threadIdx.x == 0) one_row(a0);
-  a0 += (a0 & 1);
+  const int64_t a0 = w.start;  // even (see above)
   const int64_t npair = (end - a0) >> 1;
   const ushort2* k2 = reinterpret_cast<const ushort2*>(lowkeys + a0);
   const double2* v2 = reinterpret_cast<const double2*>(vals + a0);
@@ -2691,9 +2721,6 @@ int hf_init(int gpu) {
     return set_err(HF_ERR_ARG, "hf_init", "gpu index out of range");
   HF_HIP("hf_init", hipSetDevice(gpu));
   HF_HIP("hf_init", hipStreamCreate(&g.stream));
-  HF_HIP("hf_init", hipStreamCreate(&g.stream2));
-  for (auto& ev : g.ov_ev)
-    HF_HIP("hf_init", hipEventCreateWithFlags(&ev, hipEventDisableTiming));
   HF_HIP("hf_init", hipMalloc(&g.d_scratch, SCRATCH_BYTES));
   HF_HIP("hf_init", hipMemset(g.d_scratch, 0, SCRATCH_BYTES));
   g.gpu = gpu;
@@ -2704,16 +2731,12 @@ int hf_init(int gpu) {
 int hf_shutdown(void) {
   if (!g.inited) return HF_OK;
   hipStreamSynchronize(g.stream);
-  if (g.stream2) hipStreamSynchronize(g.stream2);
   g_cache.trim();
   for (auto& p : g.pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
   g.pending.clear();
   g.stats.clear();
   if (g.d_scratch) hipFree(g.d_scratch);
-  for (auto& ev : g.ov_ev)
-    if (ev) hipEventDestroy(ev);
   hipStreamDestroy(g.stream);
-  if (g.stream2) hipStreamDestroy(g.stream2);
   g = State{};
   return HF_OK;
 }
@@ -2772,11 +2795,7 @@ int hf_get(const hf_col* col, void* host) {
 int hf_col_free(hf_col* col) {
   if (!col) return HF_OK;
   if (g.inited && col->dptr) dev_free(col->dptr, g.stream);
-  if (col->d_hist) free(col->d_hist);  // host-side cached histogram
-  if (g.inited && col->d_k32) dev_free(col->d_k32, g.stream);
-  if (g.inited && col->d_curinit) dev_free(col->d_curinit, g.stream);
-  if (g.inited && col->d_work) dev_free(col->d_work, g.stream);
-  if (g.inited) plan_free(col);
+  col->gb.release();
   delete col;
   return HF_OK;
 }
@@ -3010,41 +3029,32 @@ int ensure_host_hist(hf_col* keys, int64_t key_min, int64_t n_slots,
                      int64_t nb, int range_log) {
   // keyed on the exact n_slots, not only the bucket count: rows between two
   // n_slots inside the same last bucket change that bucket's region size
-  if (keys->d_hist && keys->hist_kmin == key_min && keys->hist_nb == nb &&
-      keys->hist_nslots == n_slots)
+  GbKeyCache& kc = keys->gb;
+  if (!kc.hist.empty() && kc.hist_kmin == key_min && kc.hist_nb == nb &&
+      kc.hist_nslots == n_slots)
     return HF_OK;
-  if (keys->d_hist) { free(keys->d_hist); keys->d_hist = nullptr; }
   // the radix layout cache and the scatter plan derive from this histogram:
   // invalidate with it
-  plan_free(keys);
-  if (keys->d_curinit) {
-    dev_free(keys->d_curinit, g.stream);
-    keys->d_curinit = nullptr;
-  }
-  if (keys->d_work) {
-    dev_free(keys->d_work, g.stream);
-    keys->d_work = nullptr;
-  }
-  keys->radix_rl = 0;
-  unsigned long long* d_h = nullptr;
-  HF_HIP("gb_hist", dev_alloc((void**)&d_h, nb * 8, g.stream));
-  HF_HIP("gb_hist", hipMemsetAsync(d_h, 0, nb * 8, g.stream));
+  kc.drop_derived();
+  DevBuf d_h;
+  HF_HIP("gb_hist", d_h.alloc(nb * 8));
+  HF_HIP("gb_hist", hipMemsetAsync(d_h.as<void>(), 0, nb * 8, g.stream));
   const int64_t n = keys->len;
   int rc = timed_launch("gb_hist", [&] {
     hipLaunchKernelGGL(k_gb_hist, dim3((uint32_t)grid_for(n)), dim3(BLOCK),
                        (uint32_t)(nb * 4), g.stream, (const int64_t*)keys->dptr,
-                       n, key_min, n_slots, (int)nb, range_log, d_h);
+                       n, key_min, n_slots, (int)nb, range_log,
+                       d_h.as<unsigned long long>());
   });
   if (rc != HF_OK) return rc;
-  int64_t* h = (int64_t*)malloc(nb * 8);
-  HF_HIP("gb_hist", hipMemcpyAsync(h, d_h, nb * 8, hipMemcpyDeviceToHost,
-                                   g.stream));
+  std::vector<int64_t> h((size_t)nb);
+  HF_HIP("gb_hist", hipMemcpyAsync(h.data(), d_h.as<void>(), nb * 8,
+                                   hipMemcpyDeviceToHost, g.stream));
   HF_HIP("gb_hist", hipStreamSynchronize(g.stream));
-  HF_HIP("gb_hist", dev_free(d_h, g.stream));
-  keys->d_hist = h;
-  keys->hist_kmin = key_min;
-  keys->hist_nb = nb;
-  keys->hist_nslots = n_slots;
+  kc.hist = std::move(h);
+  kc.hist_kmin = key_min;
+  kc.hist_nb = nb;
+  kc.hist_nslots = n_slots;
   return HF_OK;
 }
 
@@ -3077,424 +3087,299 @@ int gb_dense_path(const hf_col* keys, const GbPtrs& ptrs, int nvals,
     double* gs = (double*)sums + (int64_t)c * n_slots;
     unsigned long long* gc =
         cnt ? (unsigned long long*)counts + (int64_t)c * n_slots : nullptr;
-    int rc;
-    if (c == 0)
-      rc = cnt ? L(T{}, T{}, T{}, ptrs.vals[c], gs, gc)
-               : L(T{}, F{}, T{}, ptrs.vals[c], gs, gc);
-    else
-      rc = cnt ? L(F{}, T{}, T{}, ptrs.vals[c], gs, gc)
-               : L(F{}, F{}, T{}, ptrs.vals[c], gs, gc);
+    int rc = with_bool(c == 0, [&](auto rTag) {
+      return with_bool(cnt, [&](auto cTag) {
+        return L(rTag, cTag, T{}, ptrs.vals[c], gs, gc);
+      });
+    });
     if (rc != HF_OK) return rc;
   }
   return HF_OK;
 }
 
 int ensure_keys32(hf_col* keys, int64_t key_min) {
-  if (keys->d_k32 && keys->k32_min == key_min) return HF_OK;
-  if (keys->d_k32) { dev_free(keys->d_k32, g.stream); keys->d_k32 = nullptr; }
+  GbKeyCache& kc = keys->gb;
+  if (kc.d_k32 && kc.k32_min == key_min) return HF_OK;
+  drop_dev(kc.d_k32);
   const int64_t n = keys->len;
-  HF_HIP("keys32", dev_alloc(&keys->d_k32, (n > 0 ? n : 1) * 4, g.stream));
+  HF_HIP("keys32", dev_alloc(&kc.d_k32, (n > 0 ? n : 1) * 4, g.stream));
   int rc = timed_launch("gb_keys32", [&] {
     hipLaunchKernelGGL(k_conv_keys32, dim3((uint32_t)grid_for(n)), dim3(BLOCK),
                        0, g.stream, (const int64_t*)keys->dptr, n, key_min,
-                       (unsigned*)keys->d_k32);
+                       (unsigned*)kc.d_k32);
   });
   if (rc != HF_OK) return rc;
-  keys->k32_min = key_min;
+  kc.k32_min = key_min;
   return HF_OK;
 }
 
+// Exact per-bucket regions, 64-row aligned; u32 cursors cap one partition
+// at ~4.29e9 rows (shard larger frames).  The cursor-init array and the
+// work items derive only from the cached histogram, so they cache on the
+// immutable key column too: steady-state groupby calls copy cursors D2D
+// and never touch the host (no pageable H2D, no mid-op sync).
+// Work-item starts are off + done: off is a multiple of 64 and done a
+// multiple of AGG_CHUNK, so every start is even (k_gb_bucket_agg relies on it).
+static_assert(AGG_CHUNK % 2 == 0, "k_gb_bucket_agg needs even item starts");
+
+template <int RL>
+int ensure_radix_layout(hf_col* keys, int64_t nb) {
+  GbKeyCache& kc = keys->gb;
+  if (kc.d_curinit && kc.radix_rl == RL) return HF_OK;
+  kc.drop_derived();
+  std::vector<unsigned> cur_init((size_t)nb);
+  std::vector<GbWorkItem> work;
+  int64_t off = 0;
+  for (int64_t b = 0; b < nb; ++b) {
+    cur_init[b] = (unsigned)off;
+    const int64_t rows_b = kc.hist[b];
+    int64_t done = 0;
+    while (done < rows_b) {
+      const int64_t len = std::min(AGG_CHUNK, rows_b - done);
+      work.push_back(GbWorkItem{off + done, (int32_t)b, (int32_t)len});
+      done += len;
+    }
+    off += (rows_b + 63) & ~63LL;
+  }
+  if (off > 0xFFFFFFF0LL)
+    return set_err(HF_ERR_UNSUPPORTED, "hf_groupby_accum",
+                   "partition too large for radix scatter (shard it)");
+  DevBuf d_curinit, d_work;
+  HF_HIP("gb_radix", d_curinit.alloc(nb * 4));
+  HF_HIP("gb_radix",
+         d_work.alloc(std::max<size_t>(work.size(), 1) * sizeof(GbWorkItem)));
+  HF_HIP("gb_radix", hipMemcpyAsync(d_curinit.as<void>(), cur_init.data(),
+                                    nb * 4, hipMemcpyHostToDevice, g.stream));
+  if (!work.empty())
+    HF_HIP("gb_radix", hipMemcpyAsync(d_work.as<void>(), work.data(),
+                                      work.size() * sizeof(GbWorkItem),
+                                      hipMemcpyHostToDevice, g.stream));
+  // host vectors must outlive the async H2D of pageable memory
+  HF_HIP("gb_radix", hipStreamSynchronize(g.stream));
+  kc.d_curinit = d_curinit.release();
+  kc.d_work = d_work.release();
+  kc.work_n = (int64_t)work.size();
+  kc.radix_rows = off;
+  kc.radix_rl = RL;
+  return HF_OK;
+}
+
+// payload rows one radix call allocates (never a zero-byte block)
+int64_t radix_alloc_rows(const GbKeyCache& kc) {
+  return std::max<int64_t>(kc.radix_rows, 64);
+}
+int64_t gb_plan_tiles(int64_t n) {
+  return ((n & ~1LL) + GB_PLAN_TILE - 1) / GB_PLAN_TILE;
+}
+uint32_t gb_tile_grid(int64_t ntiles) {
+  return (uint32_t)std::min<int64_t>(std::max<int64_t>(ntiles, 1), 2048);
+}
+
+// What P1 does with the scatter plan of the key column (see GbKeyCache).
+enum class GbPlan {
+  None,    // plan-less: scatter keys + values on every call
+  Record,  // plan buffers are allocated; this call scatters and records
+  Replay,  // a valid plan exists: permute values only
+};
+
+// Valid plan -> Replay, else allocate one -> Record.  HF_GB_PLAN=0 (read
+// once) or a failed plan allocation selects the plan-less path; this never
+// fails the call.
+GbPlan ensure_plan(hf_col* keys, int rl, int64_t key_min, int64_t n_slots,
+                   int64_t nb) {
+  static const bool plan_env = [] {
+    const char* e = getenv("HF_GB_PLAN");
+    return !(e && e[0] == '0');
+  }();
+  if (!plan_env) return GbPlan::None;
+  GbKeyCache& kc = keys->gb;
+  if (kc.plan_rl == rl && kc.plan_kmin == key_min && kc.plan_nslots == n_slots)
+    return GbPlan::Replay;
+  kc.drop_plan();
+  const int64_t n = keys->len;
+  DevBuf dst, rk, tab, meta;
+  if (dst.alloc(std::max<int64_t>(n & ~1LL, 2) * 2) != hipSuccess ||
+      rk.alloc(radix_alloc_rows(kc) * 2) != hipSuccess ||
+      tab.alloc(std::max<int64_t>(gb_plan_tiles(n), 1) * (2 * nb + 1) * 4) !=
+          hipSuccess ||
+      meta.alloc(16) != hipSuccess) {
+    (void)hipGetLastError();
+    return GbPlan::None;
+  }
+  kc.d_plan_dst = dst.release();
+  kc.d_plan_rk = rk.release();
+  kc.d_plan_tab = tab.release();
+  kc.d_plan_meta = meta.release();
+  return GbPlan::Record;
+}
+
+// The arguments every P1/P2 launch of one radix call shares.
+struct GbRadixCall {
+  hf_col* keys;
+  int64_t nb, key_min, n_slots;
+  unsigned long long* d_err;
+  double* r0;          // scattered values (each column in turn on a plan)
+  double* r1;          // second column, plan-less path only
+  unsigned short* rk;  // scattered low keys (the plan's own on a plan)
+  unsigned* d_cur;     // this call's bucket cursors (none on replay)
+};
+
+// P1 scatter (pipelined): 12288-row tiles as 1024x12 for <=1 value column
+// — 147 KB LDS, 1 block/CU of 16 waves (round-2 probe: 1024x12 edges out
+// 512x24 and both beat the round-1 kernel by ~17%); 6144-row tiles as
+// 512x12 for 2 columns.
+// REC, the plan record: the scatter itself on the int64 keys (no u32 copy),
+// first value column only, at the plan's 1024x12 geometry, keeping its
+// decisions on the key column.
+template <int RL, bool REC>
+int radix_scatter(const GbRadixCall& a, const GbPtrs& ptrs, int nvals) {
+  GbKeyCache& kc = a.keys->gb;
+  const int64_t n = a.keys->len;
+  GbPlanRec rec{};
+  if (REC) {
+    unsigned long long* meta = (unsigned long long*)kc.d_plan_meta;
+    HF_HIP("gb_radix", hipMemsetAsync(meta, 0xFF, 8, g.stream));
+    HF_HIP("gb_radix", hipMemsetAsync(meta + 1, 0, 8, g.stream));
+    rec = GbPlanRec{(unsigned short*)kc.d_plan_dst, (unsigned*)kc.d_plan_tab,
+                    meta};
+  }
+  int rc = with_nvals<(REC ? 1 : 2)>(
+      REC ? std::min(nvals, 1) : nvals, [&](auto nvTag) {
+        constexpr int NV = decltype(nvTag)::value;
+        constexpr int BLK = NV < 2 ? GB_PLAN_BLK : 512;
+        constexpr int64_t TILE = (int64_t)BLK * GB_PLAN_RPT;
+        const uint32_t sgrid = gb_tile_grid(((n & ~1LL) + TILE - 1) / TILE);
+        const uint32_t lds =
+            (uint32_t)(TILE * (8 * NV + 4) + a.nb * 12 + 16);
+        return timed_launch(REC ? "gb_plan_record" : "gb_scatter", [&] {
+          hipLaunchKernelGGL(
+              (k_gb_scatter<NV, GB_PLAN_RPT, BLK, RL, REC>), dim3(sgrid),
+              dim3(BLK), lds, g.stream, (const int64_t*)a.keys->dptr,
+              (const unsigned*)kc.d_k32, ptrs.vals[0], ptrs.vals[1], n,
+              a.key_min, a.n_slots, (int)a.nb, a.d_cur, a.r0, a.r1, a.rk,
+              a.d_err, rec);
+        });
+      });
+  if (REC && rc == HF_OK) {
+    kc.plan_kmin = a.key_min;
+    kc.plan_nslots = a.n_slots;
+    kc.plan_rl = RL;
+  }
+  return rc;
+}
+
+// P1 on a recorded plan: the value permutation of one column into r0.
+int radix_replay(const GbRadixCall& a, const double* v, bool add_err) {
+  const GbKeyCache& kc = a.keys->gb;
+  const int64_t n = a.keys->len;
+  int search0 = 0;  // largest power of two <= nb - 1 (replay's first step)
+  for (int s = 1; s <= a.nb - 1; s <<= 1) search0 = s;
+  const uint32_t lds =
+      (uint32_t)((int64_t)GB_PLAN_TILE * 8 + (2 * a.nb + 1) * 4);
+  return timed_launch("gb_scatter", [&] {
+    hipLaunchKernelGGL((k_gb_replay<GB_PLAN_RPT, GB_PLAN_BLK>),
+                       dim3(gb_tile_grid(gb_plan_tiles(n))), dim3(GB_PLAN_BLK),
+                       lds, g.stream, (const unsigned short*)kc.d_plan_dst, v,
+                       n, (int)a.nb, search0, (const unsigned*)kc.d_plan_tab,
+                       (const unsigned long long*)kc.d_plan_meta, a.r0,
+                       a.d_err, add_err ? 1 : 0);
+  });
+}
+
+// A replayed call that permutes nothing (no value column, or no in-range row
+// at all) still has to carry the recorded out-of-range count to the error
+// word.
+int radix_plan_err(const GbRadixCall& a) {
+  return timed_launch("gb_plan_err", [&] {
+    hipLaunchKernelGGL(k_gb_plan_err, dim3(1), dim3(64), 0, g.stream,
+                       (const unsigned long long*)a.keys->gb.d_plan_meta,
+                       a.d_err);
+  });
+}
+
+// P2 aggregate of one scattered column (or of the keys alone).
+template <int RL, int AOP, bool R, bool C, bool V>
+int radix_agg(const GbRadixCall& a, const double* v, double* gs,
+              unsigned long long* growcnt, unsigned long long* gc) {
+  const GbKeyCache& kc = a.keys->gb;
+  return timed_launch("gb_bucket_agg", [&] {
+    hipLaunchKernelGGL((k_gb_bucket_agg<R, C, V, RL, AOP>),
+                       dim3((uint32_t)kc.work_n), dim3(512), 0, g.stream, v,
+                       a.rk, (const GbWorkItem*)kc.d_work, a.n_slots, gs,
+                       growcnt, gc);
+  });
+}
+
+// The radix groupby driver: layout -> plan mode -> P1 -> per column
+// (replay?) -> P2.  Every temporary is scoped, so any early return gives its
+// blocks back to the allocator.
 template <int RL, int AOP>
 int gb_radix_path(hf_col* keys, const GbPtrs& ptrs, int nvals, int64_t key_min,
                   int64_t n_slots, uintptr_t sums, uintptr_t rowcnt,
                   uintptr_t counts, unsigned long long* d_err,
                   bool with_rowcnt = true) {
-  const int64_t n = keys->len;
+  GbKeyCache& kc = keys->gb;
   const int64_t nb = (n_slots + (1 << RL) - 1) >> RL;
   int rc = ensure_host_hist(keys, key_min, n_slots, nb, RL);
   if (rc != HF_OK) return rc;
-  const int64_t* h = keys->d_hist ? (const int64_t*)keys->d_hist : nullptr;
-  // exact per-bucket regions, 64-row aligned; u32 cursors cap one partition
-  // at ~4.29e9 rows (shard larger frames).  The cursor-init array and the
-  // work items derive only from the cached histogram, so they cache on the
-  // immutable key column too: steady-state groupby calls copy cursors D2D
-  // and never touch the host (no pageable H2D, no mid-op sync).
-  if (!keys->d_curinit || keys->radix_rl != RL) {
-    if (keys->d_curinit) {
-      dev_free(keys->d_curinit, g.stream);
-      keys->d_curinit = nullptr;
-    }
-    if (keys->d_work) {
-      dev_free(keys->d_work, g.stream);
-      keys->d_work = nullptr;
-    }
-    std::vector<unsigned> cur_init((size_t)nb);
-    std::vector<GbWorkItem> work;
-    int64_t off = 0;
-    for (int64_t b = 0; b < nb; ++b) {
-      cur_init[b] = (unsigned)off;
-      const int64_t rows_b = h[b];
-      int64_t done = 0;
-      while (done < rows_b) {
-        const int64_t len = std::min(AGG_CHUNK, rows_b - done);
-        work.push_back(GbWorkItem{off + done, (int32_t)b, (int32_t)len});
-        done += len;
-      }
-      off += (rows_b + 63) & ~63LL;
-    }
-    if (off > 0xFFFFFFF0LL)
-      return set_err(HF_ERR_UNSUPPORTED, "hf_groupby_accum",
-                     "partition too large for radix scatter (shard it)");
-    HF_HIP("gb_radix", dev_alloc(&keys->d_curinit, nb * 4, g.stream));
-    HF_HIP("gb_radix",
-           dev_alloc(&keys->d_work,
-                     std::max<size_t>(work.size(), 1) * sizeof(GbWorkItem),
-                     g.stream));
-    HF_HIP("gb_radix", hipMemcpyAsync(keys->d_curinit, cur_init.data(),
-                                      nb * 4, hipMemcpyHostToDevice,
-                                      g.stream));
-    if (!work.empty())
-      HF_HIP("gb_radix",
-             hipMemcpyAsync(keys->d_work, work.data(),
-                            work.size() * sizeof(GbWorkItem),
-                            hipMemcpyHostToDevice, g.stream));
-    // host vectors must outlive the async H2D of pageable memory
-    HF_HIP("gb_radix", hipStreamSynchronize(g.stream));
-    keys->work_n = (int64_t)work.size();
-    keys->radix_rows = off;
-    keys->radix_rl = RL;
-  }
-  const int64_t off = keys->radix_rows;
-  GbWorkItem* d_work = (GbWorkItem*)keys->d_work;
-  const int64_t alloc_rows = off > 0 ? off : 64;
-  // HF_GB_PLAN=0 / HF_GB_OVERLAP=1 are read once; either selects the
-  // plan-less path below
-  static const bool plan_env = [] {
-    const char* e = getenv("HF_GB_PLAN");
-    return !(e && e[0] == '0');
-  }();
-  static const bool overlap_env = [] {
-    const char* e = getenv("HF_GB_OVERLAP");
-    return e && e[0] == '1';
-  }();
-  // ---- scatter plan (see hf_col): valid -> replay, else record now.  A
-  // failed plan allocation falls back to the plan-less path, never fails
-  // the call.
-  bool use_plan = plan_env && !overlap_env;
-  const bool plan_valid = use_plan && keys->plan_rl == RL &&
-                          keys->plan_kmin == key_min &&
-                          keys->plan_nslots == n_slots;
-  const int64_t plan_tiles =
-      ((n & ~1LL) + GB_PLAN_TILE - 1) / GB_PLAN_TILE;
-  const int64_t plan_tabw = 2 * nb + 1;
-  if (use_plan && !plan_valid) {
-    plan_free(keys);
-    const bool ok =
-        dev_alloc(&keys->d_plan_dst, std::max<int64_t>(n & ~1LL, 2) * 2,
-                  g.stream) == hipSuccess &&
-        dev_alloc(&keys->d_plan_rk, alloc_rows * 2, g.stream) == hipSuccess &&
-        dev_alloc(&keys->d_plan_tab,
-                  std::max<int64_t>(plan_tiles, 1) * plan_tabw * 4,
-                  g.stream) == hipSuccess &&
-        dev_alloc(&keys->d_plan_meta, 16, g.stream) == hipSuccess;
-    if (!ok) {
-      (void)hipGetLastError();
-      plan_free(keys);
-      use_plan = false;
-    }
-  }
-  if (!use_plan) {
+  rc = ensure_radix_layout<RL>(keys, nb);
+  if (rc != HF_OK) return rc;
+  const GbPlan mode = ensure_plan(keys, RL, key_min, n_slots, nb);
+  if (mode == GbPlan::None) {
     rc = ensure_keys32(keys, key_min);
     if (rc != HF_OK) return rc;
   }
-  const bool record = use_plan && !plan_valid;
-  double* r0 = nullptr;
-  double* r1 = nullptr;
-  unsigned short* rk = nullptr;
-  unsigned* d_cur = nullptr;
-  if (nvals > 0)
-    HF_HIP("gb_radix", dev_alloc((void**)&r0, alloc_rows * 8, g.stream));
-  if (nvals > 1 && !use_plan)
-    HF_HIP("gb_radix", dev_alloc((void**)&r1, alloc_rows * 8, g.stream));
-  if (use_plan)
-    rk = (unsigned short*)keys->d_plan_rk;
-  else
-    HF_HIP("gb_radix", dev_alloc((void**)&rk, alloc_rows * 2, g.stream));
-  if (!use_plan || record) {
-    HF_HIP("gb_radix", dev_alloc((void**)&d_cur, nb * 4, g.stream));
-    HF_HIP("gb_radix", hipMemcpyAsync(d_cur, keys->d_curinit, nb * 4,
+  const int64_t rows = radix_alloc_rows(kc);
+  DevBuf r0, r1, rk, d_cur;
+  if (nvals > 0) HF_HIP("gb_radix", r0.alloc(rows * 8));
+  if (mode == GbPlan::None) {
+    if (nvals > 1) HF_HIP("gb_radix", r1.alloc(rows * 8));
+    HF_HIP("gb_radix", rk.alloc(rows * 2));
+  }
+  if (mode != GbPlan::Replay) {
+    HF_HIP("gb_radix", d_cur.alloc(nb * 4));
+    HF_HIP("gb_radix", hipMemcpyAsync(d_cur.as<void>(), kc.d_curinit, nb * 4,
                                       hipMemcpyDeviceToDevice, g.stream));
   }
-
-  // ---- overlapped path: scatter in 4 chunks on the main stream; after
-  // each chunk the consumer stream aggregates the region slices that
-  // chunk completed (device-built work items from cursor snapshots).
-  // MEASURED NEGATIVE (round 2, profiles/r02): both kernels want >72 KB
-  // LDS, so concurrent scheduling PARTITIONS the CUs between them and
-  // each phase runs ~1.5x slower (uniform 9.2 ms vs 7.0 serial) — the
-  // overlap never recovers the loss.  Kept behind HF_GB_OVERLAP=1 for
-  // future experiments; default is the serial two-phase path.
-  const bool overlap =
-      overlap_env && n >= (64LL << 20) && nvals <= 2 && nb <= 1024;
-  if (overlap) {
-    const int NCH = 4;
-    const double fracs[NCH] = {0.30, 0.30, 0.30, 0.10};
-    unsigned* d_snap[NCH];
-    for (int c = 0; c < NCH; ++c)
-      HF_HIP("gb_radix", dev_alloc((void**)&d_snap[c], nb * 4, g.stream));
-    int64_t bounds[NCH + 1];
-    bounds[0] = 0;
-    double accf = 0;
-    for (int c = 0; c < NCH - 1; ++c) {
-      accf += fracs[c];
-      bounds[c + 1] = ((int64_t)(n * accf)) & ~1LL;
-    }
-    bounds[NCH] = n;
-    auto scat_chunk = [&](auto nvTag, auto rptTag, auto blkTag, int c) {
-      constexpr int NVv = decltype(nvTag)::value;
-      constexpr int RPTv = decltype(rptTag)::value;
-      constexpr int BLKv = decltype(blkTag)::value;
-      const int64_t tile_sz = (int64_t)BLKv * RPTv;
-      const int64_t rows_c = bounds[c + 1] - bounds[c];
-      const int64_t ntiles = (rows_c + tile_sz - 1) / tile_sz;
-      const uint32_t sgrid =
-          (uint32_t)std::min<int64_t>(std::max<int64_t>(ntiles, 1), 2048);
-      const uint32_t lds =
-          (uint32_t)(tile_sz * (8 * NVv + 4) + nb * 12 + 16);
-      return timed_launch("gb_scatter", [&] {
-        hipLaunchKernelGGL((k_gb_scatter<NVv, RPTv, BLKv, RL, true>),
-                           dim3(sgrid), dim3(BLKv), lds, g.stream,
-                           (const int64_t*)keys->dptr,
-                           (const unsigned*)keys->d_k32, ptrs.vals[0],
-                           ptrs.vals[1], bounds[c], bounds[c + 1], key_min,
-                           n_slots, (int)nb, d_cur, r0, r1, rk, d_err,
-                           GbPlanRec{});
-      });
-    };
-    // per-chunk device work items (k_gb_make_work) + the regular
-    // atomic-merge P2 with an upper-bound grid gated by the device count
-    GbWorkItem* d_workc[NCH];
-    int* d_nwork[NCH];
-    uint32_t ub[NCH];
-    for (int c = 0; c < NCH; ++c) {
-      const int64_t rows_c = bounds[c + 1] - bounds[c];
-      ub[c] = (uint32_t)(nb + rows_c / AGG_CHUNK + 1);
-      HF_HIP("gb_radix",
-             dev_alloc((void**)&d_workc[c], ub[c] * sizeof(GbWorkItem),
-                       g.stream));
-      HF_HIP("gb_radix", dev_alloc((void**)&d_nwork[c], 4, g.stream));
-    }
-    auto agg_chunk = [&](auto rTag, auto cTag, auto vTag, const double* v,
-                         double* gs, unsigned long long* gc, int c) {
-      constexpr bool R = decltype(rTag)::value, C = decltype(cTag)::value,
-                     V = decltype(vTag)::value;
-      return timed_launch_on("gb_bucket_agg", g.stream2, [&] {
-        hipLaunchKernelGGL((k_gb_bucket_agg<R, C, V, RL, AOP>),
-                           dim3(ub[c]), dim3(512), 0, g.stream2, v, rk,
-                           d_workc[c], d_nwork[c], n_slots, gs,
-                           (unsigned long long*)rowcnt, gc);
-      });
-    };
-    using T = std::true_type;
-    using F = std::false_type;
-    const bool cnt = counts != 0;
-    for (int c = 0; c < NCH && rc == HF_OK; ++c) {
-      rc = nvals == 0 ? scat_chunk(std::integral_constant<int, 0>{},
-                                   std::integral_constant<int, 12>{},
-                                   std::integral_constant<int, 1024>{}, c)
-           : nvals == 1 ? scat_chunk(std::integral_constant<int, 1>{},
-                                     std::integral_constant<int, 12>{},
-                                     std::integral_constant<int, 1024>{}, c)
-                        : scat_chunk(std::integral_constant<int, 2>{},
-                                     std::integral_constant<int, 12>{},
-                                     std::integral_constant<int, 512>{}, c);
-      if (rc != HF_OK) break;
-      HF_HIP("gb_radix", hipMemcpyAsync(d_snap[c], d_cur, nb * 4,
-                                        hipMemcpyDeviceToDevice, g.stream));
-      HF_HIP("gb_radix", hipEventRecord(g.ov_ev[c], g.stream));
-      HF_HIP("gb_radix", hipStreamWaitEvent(g.stream2, g.ov_ev[c], 0));
-      const unsigned* clo =
-          c == 0 ? (const unsigned*)keys->d_curinit : d_snap[c - 1];
-      const unsigned* chi = d_snap[c];
-      rc = timed_launch_on("gb_make_work", g.stream2, [&] {
-        hipLaunchKernelGGL(k_gb_make_work, dim3(1), dim3(256), 0, g.stream2,
-                           clo, chi, (int)nb, (int)AGG_CHUNK, d_workc[c],
-                           d_nwork[c]);
-      });
-      if (rc != HF_OK) break;
-      if (nvals == 0) {
-        rc = agg_chunk(T{}, F{}, F{}, nullptr, nullptr, nullptr, c);
-      } else {
-        for (int col = 0; col < nvals && rc == HF_OK; ++col) {
-          const double* v = col == 0 ? r0 : r1;
-          double* gs = (double*)sums + (int64_t)col * n_slots;
-          unsigned long long* gc =
-              cnt ? (unsigned long long*)counts + (int64_t)col * n_slots
-                  : nullptr;
-          if (col == 0 && with_rowcnt)
-            rc = cnt ? agg_chunk(T{}, T{}, T{}, v, gs, gc, c)
-                     : agg_chunk(T{}, F{}, T{}, v, gs, gc, c)
-            ;
-          else
-            rc = cnt ? agg_chunk(F{}, T{}, T{}, v, gs, gc, c)
-                     : agg_chunk(F{}, F{}, T{}, v, gs, gc, c);
-        }
-      }
-    }
-    // fence the consumer stream back onto the main stream BEFORE the
-    // payload buffers are released (keeps the allocator's single-stream
-    // reuse argument intact)
-    HF_HIP("gb_radix", hipEventRecord(g.ov_ev[NCH], g.stream2));
-    HF_HIP("gb_radix", hipStreamWaitEvent(g.stream, g.ov_ev[NCH], 0));
-    for (int c = 0; c < NCH; ++c) {
-      dev_free(d_snap[c], g.stream);
-      dev_free(d_workc[c], g.stream);
-      dev_free(d_nwork[c], g.stream);
-    }
-    if (r0) dev_free(r0, g.stream);
-    if (r1) dev_free(r1, g.stream);
-    dev_free(rk, g.stream);
-    dev_free(d_cur, g.stream);
-    return rc;
-  }
-  // P1 scatter (pipelined): 12288-row tiles as 1024x12 for <=1 value column
-  // — 147 KB LDS, 1 block/CU of 16 waves (round-2 probe: 1024x12 edges out
-  // 512x24 and both beat the round-1 kernel by ~17%); 6144-row tiles as
-  // 512x12 for 2 columns
-  auto scat = [&](auto nvTag, auto rptTag, auto blkTag) {
-    constexpr int NVv = decltype(nvTag)::value;
-    constexpr int RPTv = decltype(rptTag)::value;
-    constexpr int BLKv = decltype(blkTag)::value;
-    const int64_t tile_sz = (int64_t)BLKv * RPTv;
-    const int64_t ntiles = ((n & ~1LL) + tile_sz - 1) / tile_sz;
-    const uint32_t sgrid =
-        (uint32_t)std::min<int64_t>(std::max<int64_t>(ntiles, 1), 2048);
-    const uint32_t lds =
-        (uint32_t)(tile_sz * (8 * NVv + 4) + nb * 12 + 16);
-    return timed_launch("gb_scatter", [&] {
-      hipLaunchKernelGGL((k_gb_scatter<NVv, RPTv, BLKv, RL, true>),
-                         dim3(sgrid), dim3(BLKv), lds, g.stream,
-                         (const int64_t*)keys->dptr,
-                         (const unsigned*)keys->d_k32, ptrs.vals[0],
-                         ptrs.vals[1], (int64_t)0, n, key_min, n_slots,
-                         (int)nb, d_cur, r0, r1, rk, d_err, GbPlanRec{});
-    });
-  };
-  // plan path P1.  Record: the scatter itself on the int64 keys (no u32
-  // copy), first value column only, keeping its decisions on the hf_col.
-  // Replay: the value permutation, into the one r0 every column reuses.
-  auto plan_record = [&](auto nvTag) {
-    constexpr int NVv = decltype(nvTag)::value;
-    const uint32_t sgrid =
-        (uint32_t)std::min<int64_t>(std::max<int64_t>(plan_tiles, 1), 2048);
-    const uint32_t lds =
-        (uint32_t)((int64_t)GB_PLAN_TILE * (8 * NVv + 4) + nb * 12 + 16);
-    unsigned long long* meta = (unsigned long long*)keys->d_plan_meta;
-    HF_HIP("gb_radix", hipMemsetAsync(meta, 0xFF, 8, g.stream));
-    HF_HIP("gb_radix", hipMemsetAsync(meta + 1, 0, 8, g.stream));
-    int r = timed_launch("gb_plan_record", [&] {
-      hipLaunchKernelGGL(
-          (k_gb_scatter<NVv, GB_PLAN_RPT, GB_PLAN_BLK, RL, false, true>),
-          dim3(sgrid), dim3(GB_PLAN_BLK), lds, g.stream,
-          (const int64_t*)keys->dptr, (const unsigned*)nullptr, ptrs.vals[0],
-          (const double*)nullptr, (int64_t)0, n, key_min, n_slots, (int)nb,
-          d_cur, r0, (double*)nullptr, rk, d_err,
-          GbPlanRec{(unsigned short*)keys->d_plan_dst,
-                    (unsigned*)keys->d_plan_tab, meta});
-    });
-    if (r != HF_OK) return r;
-    keys->plan_kmin = key_min;
-    keys->plan_nslots = n_slots;
-    keys->plan_rl = RL;
-    return (int)HF_OK;
-  };
-  int search0 = 0;  // largest power of two <= nb - 1 (replay's first step)
-  for (int s = 1; s <= nb - 1; s <<= 1) search0 = s;
-  auto plan_replay = [&](const double* v, bool add_err) {
-    const uint32_t sgrid =
-        (uint32_t)std::min<int64_t>(std::max<int64_t>(plan_tiles, 1), 2048);
-    const uint32_t lds =
-        (uint32_t)((int64_t)GB_PLAN_TILE * 8 + plan_tabw * 4);
-    return timed_launch("gb_scatter", [&] {
-      hipLaunchKernelGGL((k_gb_replay<GB_PLAN_RPT, GB_PLAN_BLK>), dim3(sgrid),
-                         dim3(GB_PLAN_BLK), lds, g.stream,
-                         (const unsigned short*)keys->d_plan_dst, v, n,
-                         (int)nb, search0, (const unsigned*)keys->d_plan_tab,
-                         (const unsigned long long*)keys->d_plan_meta, r0,
-                         d_err, add_err ? 1 : 0);
-    });
-  };
-  if (!use_plan) {
-    rc = nvals == 0 ? scat(std::integral_constant<int, 0>{},
-                           std::integral_constant<int, 12>{},
-                           std::integral_constant<int, 1024>{})
-         : nvals == 1 ? scat(std::integral_constant<int, 1>{},
-                             std::integral_constant<int, 12>{},
-                             std::integral_constant<int, 1024>{})
-                      : scat(std::integral_constant<int, 2>{},
-                             std::integral_constant<int, 12>{},
-                             std::integral_constant<int, 512>{});
-  } else if (record) {
-    rc = nvals == 0 ? plan_record(std::integral_constant<int, 0>{})
-                    : plan_record(std::integral_constant<int, 1>{});
-  } else if (nvals == 0) {
-    rc = timed_launch("gb_plan_err", [&] {
-      hipLaunchKernelGGL(k_gb_plan_err, dim3(1), dim3(64), 0, g.stream,
-                         (const unsigned long long*)keys->d_plan_meta, d_err);
-    });
-  }
-  if (rc != HF_OK) return rc;
+  const GbRadixCall a{keys, nb, key_min, n_slots, d_err, r0.as<double>(),
+                      r1.as<double>(),
+                      mode == GbPlan::None ? rk.as<unsigned short>()
+                                           : (unsigned short*)kc.d_plan_rk,
+                      d_cur.as<unsigned>()};
+  // P1 (a replayed plan permutes per column, in the P2 loop below)
+  if (mode == GbPlan::None)
+    rc = radix_scatter<RL, false>(a, ptrs, nvals);
+  else if (mode == GbPlan::Record)
+    rc = radix_scatter<RL, true>(a, ptrs, nvals);
+  else if (nvals == 0 || kc.work_n == 0)
+    rc = radix_plan_err(a);
+  if (rc != HF_OK || kc.work_n == 0) return rc;
   // P2 aggregate, one column per launch
+  unsigned long long* growcnt = (unsigned long long*)rowcnt;
+  if (nvals == 0)
+    return radix_agg<RL, AOP, true, false, false>(a, nullptr, nullptr, growcnt,
+                                                  nullptr);
   const bool cnt = counts != 0;
-  const uint32_t agrid = (uint32_t)keys->work_n;
-  auto agg = [&](auto rTag, auto cTag, auto vTag, const double* v, double* gs,
-                 unsigned long long* gc) {
-    constexpr bool R = decltype(rTag)::value, C = decltype(cTag)::value,
-                   V = decltype(vTag)::value;
-    return timed_launch("gb_bucket_agg", [&] {
-      hipLaunchKernelGGL((k_gb_bucket_agg<R, C, V, RL, AOP>), dim3(agrid),
-                         dim3(512), 0, g.stream, v, rk, d_work, nullptr,
-                         n_slots, gs, (unsigned long long*)rowcnt, gc);
-    });
-  };
-  using T = std::true_type;
-  using F = std::false_type;
-  if (agrid > 0) {
-    if (nvals == 0) {
-      rc = agg(T{}, F{}, F{}, nullptr, nullptr, nullptr);
-    } else {
-      for (int c = 0; c < nvals && rc == HF_OK; ++c) {
-        // plan path: replay(column) -> agg(column) through the one r0; the
-        // record pass has already scattered column 0
-        if (use_plan && !(record && c == 0)) {
-          rc = plan_replay(ptrs.vals[c], !record && c == 0);
-          if (rc != HF_OK) break;
-        }
-        const double* v = (c == 0 || use_plan) ? r0 : r1;
-        double* gs = (double*)sums + (int64_t)c * n_slots;
-        unsigned long long* gc =
-            cnt ? (unsigned long long*)counts + (int64_t)c * n_slots : nullptr;
-        if (c == 0 && with_rowcnt)
-          rc = cnt ? agg(T{}, T{}, T{}, v, gs, gc)
-                   : agg(T{}, F{}, T{}, v, gs, gc);
-        else
-          rc = cnt ? agg(F{}, T{}, T{}, v, gs, gc)
-                   : agg(F{}, F{}, T{}, v, gs, gc);
-      }
+  for (int c = 0; c < nvals; ++c) {
+    // plan path: replay(column) -> agg(column) through the one r0; the
+    // record pass has already scattered column 0
+    if (mode == GbPlan::Replay || (mode == GbPlan::Record && c > 0)) {
+      rc = radix_replay(a, ptrs.vals[c], mode == GbPlan::Replay && c == 0);
+      if (rc != HF_OK) return rc;
     }
-  } else if (use_plan && !record && nvals > 0) {
-    // no in-range row at all: nothing to permute, but the recorded
-    // out-of-range count still has to reach the error word
-    rc = timed_launch("gb_plan_err", [&] {
-      hipLaunchKernelGGL(k_gb_plan_err, dim3(1), dim3(64), 0, g.stream,
-                         (const unsigned long long*)keys->d_plan_meta, d_err);
+    const double* v = (c == 0 || mode != GbPlan::None) ? a.r0 : a.r1;
+    double* gs = (double*)sums + (int64_t)c * n_slots;
+    unsigned long long* gc =
+        cnt ? (unsigned long long*)counts + (int64_t)c * n_slots : nullptr;
+    rc = with_bool(c == 0 && with_rowcnt, [&](auto rTag) {
+      return with_bool(cnt, [&](auto cTag) {
+        return radix_agg<RL, AOP, decltype(rTag)::value,
+                         decltype(cTag)::value, true>(a, v, gs, growcnt, gc);
+      });
     });
+    if (rc != HF_OK) return rc;
   }
-  if (r0) dev_free(r0, g.stream);
-  if (r1) dev_free(r1, g.stream);
-  if (!use_plan) dev_free(rk, g.stream);
-  if (d_cur) dev_free(d_cur, g.stream);
-  return rc;
+  return HF_OK;
 }
 
 }  // namespace
@@ -3550,59 +3435,36 @@ int hf_groupby_accum(const hf_col* keys, const hf_col* const* vals, int nvals,
         const uintptr_t ssub = sums + (uintptr_t)c0 * n_slots * 8;
         const uintptr_t csub =
             counts ? counts + (uintptr_t)c0 * n_slots * 8 : 0;
-        rc2 = rl_ok == 13
-                  ? gb_radix_path<13, AOP>(const_cast<hf_col*>(keys), sub, nv,
-                                           key_min, n_slots, ssub, rowcnt,
-                                           csub, d_err, c0 == 0)
-                  : gb_radix_path<12, AOP>(const_cast<hf_col*>(keys), sub, nv,
-                                           key_min, n_slots, ssub, rowcnt,
-                                           csub, d_err, c0 == 0);
+        auto radix = [&](auto rlTag) {
+          return gb_radix_path<decltype(rlTag)::value ? 13 : 12, AOP>(
+              const_cast<hf_col*>(keys), sub, nv, key_min, n_slots, ssub,
+              rowcnt, csub, d_err, c0 == 0);
+        };
+        rc2 = with_bool(rl_ok == 13, radix);
         if (nvals == 0) break;
       }
       return rc2;
     }
     return -1;  // fall through to the atomic path
   };
-  int routed = agg_op == HF_AGG_SUM ? route(std::integral_constant<int, HF_AGG_SUM>{})
-               : agg_op == HF_AGG_MIN ? route(std::integral_constant<int, HF_AGG_MIN>{})
-                                      : route(std::integral_constant<int, HF_AGG_MAX>{});
+  int routed = with_aop(agg_op, route);
   if (routed != -1) return routed;
-  auto launch = [&](auto nvTag, auto cntTag) {
-    constexpr int NV = decltype(nvTag)::value;
-    constexpr bool CNT = decltype(cntTag)::value;
-    auto go = [&](auto aopTag) {
-      constexpr int AOP = decltype(aopTag)::value;
-      return timed_launch("gb_accum", [&] {
-        hipLaunchKernelGGL((k_gb_accum<NV, CNT, AOP>),
-                           dim3(grid_for((n >> 1) + 1)), dim3(BLOCK), 0,
-                           g.stream, (const int64_t*)keys->dptr, ptrs, n,
-                           key_min, n_slots, (double*)sums,
-                           (unsigned long long*)rowcnt,
-                           (unsigned long long*)counts, d_err);
+  return with_nvals<GB_MAX_VALS>(nvals, [&](auto nvTag) {
+    return with_bool(counts != 0, [&](auto cntTag) {
+      return with_aop(agg_op, [&](auto aopTag) {
+        return timed_launch("gb_accum", [&] {
+          hipLaunchKernelGGL((k_gb_accum<decltype(nvTag)::value,
+                                         decltype(cntTag)::value,
+                                         decltype(aopTag)::value>),
+                             dim3(grid_for((n >> 1) + 1)), dim3(BLOCK), 0,
+                             g.stream, (const int64_t*)keys->dptr, ptrs, n,
+                             key_min, n_slots, (double*)sums,
+                             (unsigned long long*)rowcnt,
+                             (unsigned long long*)counts, d_err);
+        });
       });
-    };
-    return agg_op == HF_AGG_SUM ? go(std::integral_constant<int, HF_AGG_SUM>{})
-           : agg_op == HF_AGG_MIN ? go(std::integral_constant<int, HF_AGG_MIN>{})
-                                  : go(std::integral_constant<int, HF_AGG_MAX>{});
-  };
-  const bool cnt = counts != 0;
-  switch (nvals) {
-#define HF_GB_CASE(NV)                                                        \
-  case NV:                                                                    \
-    return cnt ? launch(std::integral_constant<int, NV>{},                    \
-                        std::integral_constant<bool, true>{})                 \
-               : launch(std::integral_constant<int, NV>{},                    \
-                        std::integral_constant<bool, false>{});
-    HF_GB_CASE(1) HF_GB_CASE(2) HF_GB_CASE(3) HF_GB_CASE(4)
-    HF_GB_CASE(5) HF_GB_CASE(6) HF_GB_CASE(7) HF_GB_CASE(8)
-#undef HF_GB_CASE
-    case 0:
-      return cnt ? launch(std::integral_constant<int, 0>{},
-                          std::integral_constant<bool, true>{})
-                 : launch(std::integral_constant<int, 0>{},
-                          std::integral_constant<bool, false>{});
-  }
-  return set_err(HF_ERR_ARG, "hf_groupby_accum", "nvals out of range");
+    });
+  });
 }
 
 int hf_group_moments(const hf_col* gid, const hf_col* val, uintptr_t centre,
@@ -3854,35 +3716,22 @@ int hf_groupby_hash_accum(const hf_col* keys, const hf_col* const* vals,
   if (n == 0) return HF_OK;
   unsigned long long* d_full =
       (unsigned long long*)((char*)g.d_scratch + SCRATCH_HASH_FULL);
-  const bool cnt = counts != 0;
-  auto launch = [&](auto nvTag, auto cTag, auto aTag) {
-    constexpr int NV = decltype(nvTag)::value;
-    constexpr bool C = decltype(cTag)::value;
-    constexpr int A = decltype(aTag)::value;
-    return timed_launch("gb_hash_accum", [&] {
-      hipLaunchKernelGGL((k_gb_hash_accum<NV, C, A>),
-                         dim3((uint32_t)grid_for(n)), dim3(BLOCK), 0, g.stream,
-                         (const int64_t*)keys->dptr, ptrs, n, H,
-                         (long long*)tkey, (double*)sums,
-                         (unsigned long long*)rowcnt,
-                         (unsigned long long*)counts, d_full);
+  return with_nvals<GB_MAX_VALS>(nvals, [&](auto nvTag) {
+    return with_bool(counts != 0, [&](auto cTag) {
+      return with_aop(agg_op, [&](auto aTag) {
+        return timed_launch("gb_hash_accum", [&] {
+          hipLaunchKernelGGL((k_gb_hash_accum<decltype(nvTag)::value,
+                                              decltype(cTag)::value,
+                                              decltype(aTag)::value>),
+                             dim3((uint32_t)grid_for(n)), dim3(BLOCK), 0,
+                             g.stream, (const int64_t*)keys->dptr, ptrs, n, H,
+                             (long long*)tkey, (double*)sums,
+                             (unsigned long long*)rowcnt,
+                             (unsigned long long*)counts, d_full);
+        });
+      });
     });
-  };
-  auto withA = [&](auto nvTag, auto cTag) {
-    return agg_op == HF_AGG_SUM
-               ? launch(nvTag, cTag, std::integral_constant<int, HF_AGG_SUM>{})
-           : agg_op == HF_AGG_MIN
-               ? launch(nvTag, cTag, std::integral_constant<int, HF_AGG_MIN>{})
-               : launch(nvTag, cTag,
-                        std::integral_constant<int, HF_AGG_MAX>{});
-  };
-  switch (nvals) {
-#define HF_GH_CASE(NV)                                                          case NV:                                                                        return cnt ? withA(std::integral_constant<int, NV>{},                                            std::integral_constant<bool, true>{})                                 : withA(std::integral_constant<int, NV>{},                                            std::integral_constant<bool, false>{});
-    HF_GH_CASE(0) HF_GH_CASE(1) HF_GH_CASE(2) HF_GH_CASE(3) HF_GH_CASE(4)
-    HF_GH_CASE(5) HF_GH_CASE(6) HF_GH_CASE(7) HF_GH_CASE(8)
-#undef HF_GH_CASE
-  }
-  return set_err(HF_ERR_ARG, "hf_groupby_hash_accum", "nvals out of range");
+  });
 }
 
 int hf_groupby_hash_compact(uintptr_t tkey, uintptr_t sums, uintptr_t rowcnt,
@@ -4226,6 +4075,8 @@ int hf_groupby_sorted(const hf_col* sorted_keys, const hf_col* const* vals,
   hf_col* head = nullptr;
   int rc = hf_col_alloc(n, HF_INT64, &head);
   if (rc != HF_OK) return rc;
+  const std::unique_ptr<hf_col, int (*)(hf_col*)> head_owner(head,
+                                                             hf_col_free);
   if (n > 0) {
     rc = timed_launch("gb_sorted_heads", [&] {
       hipLaunchKernelGGL(k_head_flags, dim3((uint32_t)grid_for(n)),
@@ -4233,117 +4084,91 @@ int hf_groupby_sorted(const hf_col* sorted_keys, const hf_col* const* vals,
                          (const int64_t*)sorted_keys->dptr, n,
                          (long long*)head->dptr);
     });
-    if (rc != HF_OK) { hf_col_free(head); return rc; }
+    if (rc != HF_OK) return rc;
   }
   hf_filterplan* plan = nullptr;
   int64_t C = 0;
   rc = hf_filter_plan(head, &plan, &C);
-  if (rc != HF_OK) { hf_col_free(head); return rc; }
+  if (rc != HF_OK) return rc;
+  const std::unique_ptr<hf_filterplan, int (*)(hf_filterplan*)> plan_owner(
+      plan, hf_filter_plan_free);
   // outputs: unique keys (filter of sorted keys) + per-run aggregates
   rc = hf_filter_apply(plan, sorted_keys, out_keys);
+  if (rc != HF_OK) return rc;
   const bool cnt = want_counts != 0;
   // per-run aggregate buffers
   const int64_t Ca = C > 0 ? C : 1;
-  double* gsums = nullptr;
-  unsigned long long* growcnt = nullptr;
-  unsigned long long* gcounts = nullptr;
-  if (rc == HF_OK)
+  DevBuf gsums_buf, growcnt_buf, gcounts_buf;
+  HF_HIP("hf_groupby_sorted", gsums_buf.alloc(Ca * 8 * (nvals ? nvals : 1)));
+  HF_HIP("hf_groupby_sorted", growcnt_buf.alloc(Ca * 8));
+  if (cnt)
     HF_HIP("hf_groupby_sorted",
-           dev_alloc((void**)&gsums, Ca * 8 * (nvals ? nvals : 1), g.stream));
-  if (rc == HF_OK)
-    HF_HIP("hf_groupby_sorted", dev_alloc((void**)&growcnt, Ca * 8, g.stream));
-  if (rc == HF_OK && cnt)
-    HF_HIP("hf_groupby_sorted",
-           dev_alloc((void**)&gcounts, Ca * 8 * (nvals ? nvals : 1), g.stream));
-  if (rc == HF_OK) {
+           gcounts_buf.alloc(Ca * 8 * (nvals ? nvals : 1)));
+  double* gsums = gsums_buf.as<double>();
+  unsigned long long* growcnt = growcnt_buf.as<unsigned long long>();
+  unsigned long long* gcounts = gcounts_buf.as<unsigned long long>();
+  if (nvals) {
     const double init =
         agg_op == HF_AGG_SUM ? 0.0
         : agg_op == HF_AGG_MIN ? __builtin_huge_val() : -__builtin_huge_val();
-    if (nvals) {
-      rc = timed_launch("fill_f64", [&] {
-        hipLaunchKernelGGL(k_fill_f64,
-                           dim3((uint32_t)grid_for(Ca * nvals)), dim3(BLOCK),
-                           0, g.stream, gsums, init, Ca * nvals);
-      });
-    }
-    HF_HIP("hf_groupby_sorted", hipMemsetAsync(growcnt, 0, Ca * 8, g.stream));
-    if (cnt && nvals)
-      HF_HIP("hf_groupby_sorted",
-             hipMemsetAsync(gcounts, 0, Ca * 8 * nvals, g.stream));
+    rc = timed_launch("fill_f64", [&] {
+      hipLaunchKernelGGL(k_fill_f64, dim3((uint32_t)grid_for(Ca * nvals)),
+                         dim3(BLOCK), 0, g.stream, gsums, init, Ca * nvals);
+    });
+    if (rc != HF_OK) return rc;
   }
+  HF_HIP("hf_groupby_sorted", hipMemsetAsync(growcnt, 0, Ca * 8, g.stream));
+  if (cnt && nvals)
+    HF_HIP("hf_groupby_sorted",
+           hipMemsetAsync(gcounts, 0, Ca * 8 * nvals, g.stream));
   // aggregate per column (ROWCNT on the first launch only)
   const int64_t ntiles = n > 0 ? (n + FILT_TILE - 1) / FILT_TILE : 1;
-  auto seg = [&](auto aTag, auto cTag, auto rTag, auto vTag, const double* v,
-                 double* gs, unsigned long long* gc) {
-    constexpr int A = decltype(aTag)::value;
-    constexpr bool CC = decltype(cTag)::value;
-    constexpr bool R = decltype(rTag)::value;
-    constexpr bool V = decltype(vTag)::value;
-    return timed_launch("gb_segagg", [&] {
-      hipLaunchKernelGGL((k_segagg<A, CC, R, V>), dim3((uint32_t)ntiles),
-                         dim3(BLOCK), 0, g.stream, (const long long*)head->dptr,
-                         v, n, plan_tiles(plan), gs, growcnt, gc);
-    });
-  };
-  using T = std::true_type;
-  using F = std::false_type;
-  auto segA = [&](auto cTag, auto rTag, auto vTag, const double* v, double* gs,
-                  unsigned long long* gc) {
-    return agg_op == HF_AGG_SUM
-               ? seg(std::integral_constant<int, HF_AGG_SUM>{}, cTag, rTag,
-                     vTag, v, gs, gc)
-           : agg_op == HF_AGG_MIN
-               ? seg(std::integral_constant<int, HF_AGG_MIN>{}, cTag, rTag,
-                     vTag, v, gs, gc)
-               : seg(std::integral_constant<int, HF_AGG_MAX>{}, cTag, rTag,
-                     vTag, v, gs, gc);
-  };
-  if (rc == HF_OK && n > 0) {
-    if (nvals == 0) {
-      rc = segA(F{}, T{}, F{}, nullptr, nullptr, nullptr);
-    } else {
-      for (int c = 0; c < nvals && rc == HF_OK; ++c) {
+  if (n > 0) {
+    rc = with_aop(agg_op, [&](auto aTag) {
+      auto seg = [&](auto cTag, auto rTag, auto vTag, const double* v,
+                     double* gs, unsigned long long* gc) {
+        return timed_launch("gb_segagg", [&] {
+          hipLaunchKernelGGL(
+              (k_segagg<decltype(aTag)::value, decltype(cTag)::value,
+                        decltype(rTag)::value, decltype(vTag)::value>),
+              dim3((uint32_t)ntiles), dim3(BLOCK), 0, g.stream,
+              (const long long*)head->dptr, v, n, plan_tiles(plan), gs,
+              growcnt, gc);
+        });
+      };
+      using T = std::true_type;
+      using F = std::false_type;
+      if (nvals == 0) return seg(F{}, T{}, F{}, nullptr, nullptr, nullptr);
+      for (int c = 0; c < nvals; ++c) {
         double* gs = gsums + (int64_t)c * Ca;
         unsigned long long* gc = cnt ? gcounts + (int64_t)c * Ca : nullptr;
         const double* v = (const double*)vals[c]->dptr;
-        if (c == 0)
-          rc = cnt ? segA(T{}, T{}, T{}, v, gs, gc)
-                   : segA(F{}, T{}, T{}, v, gs, gc);
-        else
-          rc = cnt ? segA(T{}, F{}, T{}, v, gs, gc)
-                   : segA(F{}, F{}, T{}, v, gs, gc);
+        const int r = with_bool(cnt, [&](auto cTag) {
+          return with_bool(c == 0, [&](auto rTag) {
+            return seg(cTag, rTag, T{}, v, gs, gc);
+          });
+        });
+        if (r != HF_OK) return r;
       }
-    }
+      return (int)HF_OK;
+    });
+    if (rc != HF_OK) return rc;
   }
-  // wrap aggregate buffers as columns (transfer ownership)
-  for (int c = 0; c < nvals && rc == HF_OK; ++c) {
-    hf_col* sc = new hf_col{};
-    sc->len = C;
-    sc->dtype = HF_FLOAT64;
-    sc->gpu = g.gpu;
-    HF_HIP("hf_groupby_sorted", dev_alloc(&sc->dptr, Ca * 8, g.stream));
+  // copy the aggregates out as columns
+  for (int c = 0; c < nvals; ++c) {
+    rc = hf_col_alloc(C, HF_FLOAT64, &out_sums[c]);
+    if (rc != HF_OK) return rc;
     HF_HIP("hf_groupby_sorted",
-           hipMemcpyAsync(sc->dptr, gsums + (int64_t)c * Ca, Ca * 8,
+           hipMemcpyAsync(out_sums[c]->dptr, gsums + (int64_t)c * Ca, Ca * 8,
                           hipMemcpyDeviceToDevice, g.stream));
-    out_sums[c] = sc;
     if (cnt && out_counts) {
-      hf_col* cc2 = new hf_col{};
-      cc2->len = C;
-      cc2->dtype = HF_INT64;
-      cc2->gpu = g.gpu;
-      HF_HIP("hf_groupby_sorted", dev_alloc(&cc2->dptr, Ca * 8, g.stream));
+      rc = hf_col_alloc(C, HF_INT64, &out_counts[c]);
+      if (rc != HF_OK) return rc;
       HF_HIP("hf_groupby_sorted",
-             hipMemcpyAsync(cc2->dptr, gcounts + (int64_t)c * Ca, Ca * 8,
-                            hipMemcpyDeviceToDevice, g.stream));
-      out_counts[c] = cc2;
+             hipMemcpyAsync(out_counts[c]->dptr, gcounts + (int64_t)c * Ca,
+                            Ca * 8, hipMemcpyDeviceToDevice, g.stream));
     }
   }
-  hf_filter_plan_free(plan);
-  hf_col_free(head);
-  if (gsums) dev_free(gsums, g.stream);
-  if (growcnt) dev_free(growcnt, g.stream);
-  if (gcounts) dev_free(gcounts, g.stream);
-  if (rc != HF_OK) return rc;
   *n_groups = C;
   return HF_OK;
 }

@@ -195,6 +195,24 @@ def test_key_distributions(dist):
     _rounds(keys, kmin, span, [1, 1, 2], rng, nan_frac=0.05)
 
 
+def test_bucket_split_into_two_work_items_with_odd_tail():
+    """One bucket above AGG_CHUNK (2^21 rows per aggregate work item) is split
+    into two items; its odd row count leaves the second item an odd tail.
+    Bucket 0 takes every row but 101 drawn ones and the pinned last row, which
+    land in the last bucket.  Keys stay below 4096, so bucket 0 is the same
+    with counts (4096-key buckets) as without (8192)."""
+    agg_chunk = 2**21
+    rng = np.random.default_rng(70)
+    n, span, kmin = 2**21 + 2**20 + 3, 8192 + 300, -5
+    keys = rng.integers(kmin, kmin + 4096, n).astype(np.int64)
+    keys[rng.choice(np.arange(1, n - 1), 101, replace=False)] = \
+        rng.integers(kmin + 8192, kmin + span, 101)
+    keys[0], keys[n - 1] = kmin, kmin + span - 1  # pinned ends: n_slots == span
+    in_b0 = int((keys - kmin < 4096).sum())
+    assert in_b0 == n - 102 and in_b0 % 2 == 1 and in_b0 > agg_chunk
+    _rounds(keys, kmin, span, [1, 2], rng, counts_seq=[0, 1], nan_frac=0.05)
+
+
 def test_out_of_range_key_raises_on_record_and_on_replay():
     rng = np.random.default_rng(50)
     span, kmin = 8192 + 300, 0
