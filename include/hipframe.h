@@ -367,6 +367,35 @@ int hf_cumsum(const hf_col* col, int agg_op, hf_col** out);
 int hf_seg_cumsum(const hf_col* col, const hf_col* heads, int agg_op,
                   hf_col** out);
 
+/* Exponentially weighted mean down the column: pandas ewm(alpha=...,
+ * adjust, ignore_na, min_periods).mean().  The reference sends every ewm to
+ * pandas (_default_to_pandas, modin/pandas/base.py:1645 and
+ * modin/pandas/groupby.py:493); this is the device form.
+ *
+ * With d = 1 - alpha, each segment keeps a state (y, w, nobs) and walks its
+ * rows in order (NaN is the missing value; int64 rows are all valid):
+ *   first valid row:   y = x, w = 1
+ *   later valid row:   ow = w*d;  nw = adjust ? 1 : alpha;
+ *                      y = (ow*y + nw*x) / (ow + nw);
+ *                      w = adjust ? ow + nw : 1
+ *   NaN row after a valid one:  w *= d   (unchanged when ignore_na)
+ *   every row, NaN rows included, emits y if nobs >= max(min_periods, 1),
+ *   else NaN — so a NaN row carries the last mean forward.
+ * nobs counts the segment's valid rows so far.  A row whose `heads` entry
+ * is nonzero (int64 0/1 column, same length) starts a new segment with an
+ * empty state; heads == NULL is one segment.  col is HF_FLOAT64 or
+ * HF_INT64, *out is HF_FLOAT64 of the same length (empty for an empty col).
+ * HF_ERR_ARG: null col/out, alpha outside (0, 1], min_periods < 0, a heads
+ * column of another length or dtype, an unsupported col dtype.
+ *
+ * Device: two chained affine recurrences (weights, then mean) under the
+ * ordered combine (a1,b1) then (a2,b2) = (a2*a1, a2*b1 + b2), each a
+ * three-phase tile scan; no numerator/denominator sums, so alpha = 1 and
+ * underflowing NaN gaps carry forward exactly as pandas does. */
+int hf_ewm_mean(const hf_col* col, const hf_col* heads /* nullable */,
+                double alpha, int adjust, int ignore_na, int64_t min_periods,
+                hf_col** out);
+
 /* Inverse-permutation scatter: out[idx[i]] = col[i]; idx must be a
  * permutation of [0, len) (a hf_sort_perm result).  Restores original row
  * order after a sort-then-transform composition — the device analog of the

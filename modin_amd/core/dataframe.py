@@ -2367,6 +2367,142 @@ class HipDataframe:
                             pandas.Series({c: np.dtype(np.float64)
                                            for c in names}))
 
+    # ---- exponentially weighted mean (pandas ewm(...).mean(); the
+    # reference defaults to pandas: modin/pandas/base.py:1645,
+    # modin/pandas/groupby.py:493).  One hf_ewm_mean call per column: the
+    # chained weight/mean recurrence scan (include/hipframe.h) ----
+    def _ewm_gates(self, val_names) -> None:
+        self._single_rank_only("ewm")
+        blk_cats = (self._partitions[0].block().cats
+                    if self._partitions else {})
+        dtc = self._dt_cols()
+        for v in val_names:
+            if v in blk_cats:
+                raise lib.HfError(f"ewm over string column {v!r} (pandas "
+                                  "raises on non-numeric data too)")
+            if v in dtc:
+                raise lib.HfError(f"ewm over datetime column {v!r} "
+                                  "(pandas is numeric-only here too)")
+        if not isinstance(self._index, pandas.RangeIndex) or \
+                self._index.start != 0 or self._index.step != 1:
+            raise lib.HfError("ewm: only RangeIndex frames this round")
+
+    def ewm_mean(self, alpha: float, adjust: bool = True,
+                 ignore_na: bool = False, min_periods: int = 0
+                 ) -> "HipDataframe":
+        """pandas ewm(alpha, adjust, ignore_na, min_periods).mean() down
+        every column; results float64, NaN rows carry the last mean."""
+        names = list(self.columns)
+        self._ewm_gates(names)
+        n = len(self)
+        dts = pandas.Series({c: np.dtype(np.float64) for c in names})
+        if n == 0:
+            part = HipDataframePartition(DeviceBlock(
+                {c: lib.alloc(0, lib.HF_FLOAT64) for c in names}, 0))
+            return HipDataframe([part], pandas.RangeIndex(0), names, [0],
+                                dts)
+        out_cols = {}
+        for c in names:
+            cols = [p.block().columns[c] for p in self._partitions]
+            vc = cols[0] if len(cols) == 1 else lib.concat(cols)
+            out_cols[c] = lib.ewm_mean(vc, None, alpha, adjust, ignore_na,
+                                       min_periods)
+        part = HipDataframePartition(DeviceBlock(out_cols, n))
+        return HipDataframe([part], pandas.RangeIndex(n), names, [n], dts)
+
+    def groupby_ewm_mean(self, by, alpha: float, adjust: bool = True,
+                         ignore_na: bool = False, min_periods: int = 0
+                         ) -> "HipDataframe":
+        """pandas groupby(by).ewm(...).mean(): rows in GROUP order (sorted
+        keys, original order within a group) under a MultiIndex of
+        (key levels..., original row label), key columns excluded, rows
+        with a NaN/NaT key dropped (dropna=True).
+
+        The groupby_transform recipe without the scatter back: drop the
+        invalid-key rows, stable sort by the effective keys, key-run head
+        flags, then hf_ewm_mean over the key-sorted values with those
+        heads.  The index is built on the host from the gathered keys and
+        the permutation."""
+        by_list = [by] if isinstance(by, str) else list(by)
+        for b in by_list:
+            if b not in self.columns:
+                raise lib.HfError(f"groupby: key column {b!r} missing")
+        val_names = [c for c in self.columns if c not in by_list]
+        self._ewm_gates(val_names)
+        blk_cats = (self._partitions[0].block().cats
+                    if self._partitions else {})
+        dtc = self._dt_cols()
+        n = len(self)
+
+        def concat_col(name):
+            cols = [p.block().columns[name] for p in self._partitions]
+            return cols[0] if len(cols) == 1 else lib.concat(cols)
+
+        key_cols = {b: concat_col(b) for b in by_list} if n else {}
+        val_cols = {v: concat_col(v) for v in val_names} if n else {}
+        pos = self._iota(n) if n else None
+        valid = None
+        for b in by_list if n else []:
+            c = key_cols[b]
+            if b in blk_cats:
+                m = lib.compare_scalar(lib.CMP_GE, c, 0.0)
+            elif c.dtype_code == lib.HF_FLOAT64:
+                m = lib.compare_scalar(lib.CMP_NOTNA, c, 0.0)
+            elif b in dtc:
+                m = lib.compare_scalar(lib.CMP_NE, c, float(INAT))
+            else:
+                continue
+            valid = m if valid is None else lib.binary(lib.BIN_MUL, valid, m)
+        if valid is not None and lib.reduce(valid).isum < n:
+            plan = lib.filter_plan(valid)
+            n = plan.n_kept
+            key_cols = {b: lib.filter_apply(plan, c)
+                        for b, c in key_cols.items()}
+            val_cols = {v: lib.filter_apply(plan, c)
+                        for v, c in val_cols.items()}
+            pos = lib.filter_iota(plan, 0)
+        dts = pandas.Series({v: np.dtype(np.float64) for v in val_names})
+
+        def key_level(b, arr):
+            if b in blk_cats:
+                from .partition import decode_dict
+                return decode_dict(arr, blk_cats[b])
+            if b in dtc:
+                return arr.view("datetime64[ns]")
+            return arr
+
+        if n == 0:
+            levels = [key_level(b, np.empty(0, dtype=self.dtypes[b]
+                                            if b not in blk_cats and
+                                            b not in dtc else np.int64))
+                      for b in by_list]
+            index = pandas.MultiIndex.from_arrays(
+                levels + [np.empty(0, dtype=np.int64)],
+                names=by_list + [None])
+            part = HipDataframePartition(DeviceBlock(
+                {v: lib.alloc(0, lib.HF_FLOAT64) for v in val_names}, 0))
+            return HipDataframe([part], index, val_names, [0], dts)
+        eff_keys = [self._effective_sort_key(key_cols[b], b in blk_cats,
+                                             True) for b in by_list]
+        perm = self._compose_sort_perm(eff_keys)
+        head = None
+        for ekc, _ in eff_keys:
+            h = self._run_head_col(lib.gather(ekc, perm), n)
+            head = h if head is None else lib.binary(lib.BIN_ADD, head, h)
+        if len(eff_keys) > 1:
+            head = lib.compare_scalar(lib.CMP_GE, head, 1.0)
+        out_cols = {}
+        for v in val_names:
+            out_cols[v] = lib.ewm_mean(lib.gather(val_cols[v], perm), head,
+                                       alpha, adjust, ignore_na, min_periods)
+        levels = [key_level(b, lib.get(lib.gather(key_cols[b], perm)))
+                  for b in by_list]
+        index = pandas.MultiIndex.from_arrays(
+            levels + [lib.get(lib.gather(pos, perm))],
+            names=by_list + [None])
+        part = HipDataframePartition(DeviceBlock(out_cols, n))
+        return HipDataframe([part], index, val_names, [n], dts)
+
     def dt_field(self, field: str) -> "HipDataframe":
         """Series.dt.<field> over datetime64[ns] typed columns: exact
         int64 calendar math on the ns view (Howard Hinnant's civil-from-

@@ -144,6 +144,9 @@ def load() -> ct.CDLL:
                                      ct.POINTER(ct.c_void_p)]),
             "hf_seg_cumsum": (ct.c_int, [ct.c_void_p, ct.c_void_p, ct.c_int,
                                          ct.POINTER(ct.c_void_p)]),
+            "hf_ewm_mean": (ct.c_int, [ct.c_void_p, ct.c_void_p, ct.c_double,
+                                       ct.c_int, ct.c_int, ct.c_int64,
+                                       ct.POINTER(ct.c_void_p)]),
             "hf_scatter": (ct.c_int, [ct.c_void_p, ct.c_void_p,
                                       ct.POINTER(ct.c_void_p)]),
             "hf_cross_idx": (ct.c_int, [ct.c_int64, ct.c_int64,
@@ -216,7 +219,7 @@ def exported_symbols():
         "hf_groupby_hash_accum", "hf_groupby_hash_compact",
         "hf_groupby_sorted", "hf_shuffle_dest", "hf_memcpy_dd",
         "hf_search_sorted", "hf_ordered_i64", "hf_cumsum", "hf_seg_cumsum",
-        "hf_scatter", "hf_cross_idx",
+        "hf_ewm_mean", "hf_scatter", "hf_cross_idx",
         "hf_col_concat", "hf_col_slice", "hf_join_build", "hf_join_free", "hf_join_probe",
         "hf_gather", "hf_compare_scalar", "hf_filter_plan", "hf_filter_apply",
         "hf_filter_iota", "hf_filter_plan_free", "hf_profiling",
@@ -706,6 +709,22 @@ def seg_cumsum(col: ColumnRef, heads: ColumnRef,
     _check(load().hf_seg_cumsum(col.handle, heads.handle, agg_op,
                                 ct.byref(out)), "hf_seg_cumsum")
     return _wrap(out, col.length, col.dtype_code)
+
+
+def ewm_mean(col: ColumnRef, heads, alpha: float, adjust: bool = True,
+             ignore_na: bool = False, min_periods: int = 0) -> ColumnRef:
+    """Exponentially weighted mean down the column (pandas
+    ewm(alpha=...).mean()), restarting at rows whose `heads` entry is
+    nonzero; heads=None is one segment.  f64 NaN rows carry the last mean
+    forward; the result is float64."""
+    ensure_ready()
+    out = ct.c_void_p()
+    _check(load().hf_ewm_mean(col.handle,
+                              None if heads is None else heads.handle,
+                              float(alpha), 1 if adjust else 0,
+                              1 if ignore_na else 0, int(min_periods),
+                              ct.byref(out)), "hf_ewm_mean")
+    return _wrap(out, col.length, HF_FLOAT64)
 
 
 def cross_idx(nl: int, nr: int):

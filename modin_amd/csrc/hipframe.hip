@@ -2668,6 +2668,269 @@ __global__ void __launch_bounds__(BLOCK) k_seg_apply(
   }
 }
 
+// ---------------------------------------------------------------------------
+// Exponentially weighted mean (pandas ewm(...).mean(); hf_ewm_mean in the
+// header states the row-by-row state machine).  Two CHAINED first-order
+// linear recurrences, both scanned as affine maps under the one ordered,
+// division-free combine
+//   (a1,b1) then (a2,b2) = (a2*a1, a2*b1 + b2)
+//   weights  W_t = P_t W_{t-1} + Q_t   (plus nobs_t, the segmented count of
+//                                       valid rows, in the same state)
+//   mean     M_t = A_t M_{t-1} + B_t   with A_t, B_t built per row from
+//                                       W_{t-1} and nobs_{t-1}
+// A numerator/denominator scan is NOT used: alpha = 1 and any NaN gap long
+// enough for d^gap to underflow make it 0/0 where pandas carries the last
+// mean forward.  Here the only division is per row by ow + nw >= nw > 0.
+// Five launches: weight tile summaries, exclusive tile scan, mean tile
+// summaries (each tile rebuilds W/nobs from its entry state), exclusive tile
+// scan, apply.  Like the segmented scan the combine is not commutative, so
+// every fold is an ordered left-to-right pass: per thread over PER
+// consecutive rows, wave-level shfl_up scan, then the wave totals in order.
+// ---------------------------------------------------------------------------
+struct EwW {  // weight map (p, q) + segmented valid-row count (keep, cnt)
+  double p, q;
+  long long cnt, keep;
+  static __device__ __forceinline__ EwW ident() { return {1.0, 0.0, 0, 1}; }
+  static __device__ __forceinline__ EwW then(const EwW& f, const EwW& g) {
+    return {g.p * f.p, g.p * f.q + g.q, g.keep ? f.cnt + g.cnt : g.cnt,
+            f.keep & g.keep};
+  }
+  __device__ __forceinline__ EwW shfl_up(int off) const {
+    return {__shfl_up(p, off), __shfl_up(q, off), __shfl_up(cnt, off),
+            __shfl_up(keep, off)};
+  }
+};
+struct EwM {  // mean map (a, b)
+  double a, b;
+  static __device__ __forceinline__ EwM ident() { return {1.0, 0.0}; }
+  static __device__ __forceinline__ EwM then(const EwM& f, const EwM& g) {
+    return {g.a * f.a, g.a * f.b + g.b};
+  }
+  __device__ __forceinline__ EwM shfl_up(int off) const {
+    return {__shfl_up(a, off), __shfl_up(b, off)};
+  }
+};
+struct EwPar {
+  double d;       // 1 - alpha
+  double nw;      // weight of a new observation: 1 (adjust) or alpha
+  double pval;    // P of a valid row: d (adjust) or 0
+  double pnan;    // P of a NaN row: d, or 1 under ignore_na
+  long long thresh;  // emit when nobs >= thresh = max(min_periods, 1)
+};
+
+// Ordered exclusive scan of one S per thread over an NT-thread block; *total
+// receives the whole block's fold in every thread.  wtot is NT/64 shared
+// slots, free for reuse on return.
+template <typename S, int NT>
+__device__ __forceinline__ S ew_block_excl(S v, S* wtot, S* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int off = 1; off < 64; off <<= 1) {
+    const S prev = v.shfl_up(off);
+    if (lane >= off) v = S::then(prev, v);
+  }
+  if (lane == 63) wtot[wave] = v;
+  S ex = v.shfl_up(1);
+  if (lane == 0) ex = S::ident();
+  __syncthreads();
+  S pre = S::ident(), tot = S::ident();
+  for (int w = 0; w < NT / 64; ++w) {
+    if (w == wave) pre = tot;
+    tot = S::then(tot, wtot[w]);
+  }
+  *total = tot;
+  __syncthreads();
+  return S::then(pre, ex);
+}
+
+constexpr int EW_PER = FILT_TILE / BLOCK;
+// LDS slot of tile row i: one pad double per thread run keeps the per-thread
+// sequential walks (stride EW_PER doubles between lanes) off the same banks
+__device__ __forceinline__ int ew_slot(int i) { return i + i / EW_PER; }
+constexpr int EW_STAGE = FILT_TILE + BLOCK;
+
+// coalesced tile load into LDS; int64 values convert here
+template <typename T, bool HEADS>
+__device__ __forceinline__ void ew_stage(
+    const T* __restrict__ in, const int64_t* __restrict__ heads, int64_t t0,
+    int64_t t1, double* sv, unsigned char* sf) {
+  for (int j = 0; j < EW_PER; ++j) {
+    const int64_t i = t0 + (int64_t)j * BLOCK + threadIdx.x;
+    if (i < t1) {
+      sv[ew_slot((int)(i - t0))] = (double)in[i];
+      if (HEADS) sf[(int)(i - t0)] = heads[i] != 0;
+    }
+  }
+  __syncthreads();
+}
+
+// the weight/count map of one thread's run of rows [s0, s0 + EW_PER)
+template <bool HEADS>
+__device__ __forceinline__ EwW ew_w_fold(const double* sv,
+                                         const unsigned char* sf, int s0,
+                                         int lim, const EwPar& k) {
+  EwW s = EwW::ident();
+#pragma unroll
+  for (int j = 0; j < EW_PER; ++j) {
+    if (s0 + j < lim) {
+      const double x = sv[ew_slot(s0 + j)];
+      const bool valid = x == x;
+      double p = valid ? k.pval : k.pnan;
+      if (HEADS && sf[s0 + j]) { p = 0.0; s.keep = 0; s.cnt = 0; }
+      s.p *= p;
+      s.q = p * s.q + (valid ? 1.0 : 0.0);
+      s.cnt += valid;
+    }
+  }
+  return s;
+}
+
+// One row: advance (W, nobs) and return the row's mean map.
+__device__ __forceinline__ EwM ew_row(double x, bool head, double& W,
+                                      long long& nobs, const EwPar& k) {
+  if (head) { W = 0.0; nobs = 0; }
+  EwM m;
+  if (x == x) {
+    const double ow = k.d * W;
+    if (nobs == 0) {
+      m.a = 0.0;
+      m.b = x;
+    } else {
+      const double s = ow + k.nw;
+      m.a = ow / s;
+      m.b = k.nw * x / s;
+    }
+    W = k.pval * W + 1.0;
+    nobs += 1;
+  } else {
+    m.a = head ? 0.0 : 1.0;
+    m.b = 0.0;
+    W *= k.pnan;
+  }
+  return m;
+}
+
+template <typename T, bool HEADS>
+__global__ void __launch_bounds__(BLOCK) k_ewm_w_tiles(
+    const T* __restrict__ in, const int64_t* __restrict__ heads, int64_t n,
+    EwPar k, EwW* __restrict__ tile_w) {
+  const int64_t t0 = (int64_t)blockIdx.x * FILT_TILE;
+  const int64_t t1 = min(t0 + (int64_t)FILT_TILE, n);
+  __shared__ double sv[EW_STAGE];
+  __shared__ unsigned char sf[HEADS ? FILT_TILE : 1];
+  __shared__ EwW wtot[BLOCK / 64];
+  ew_stage<T, HEADS>(in, heads, t0, t1, sv, sf);
+  const EwW s = ew_w_fold<HEADS>(sv, sf, threadIdx.x * EW_PER,
+                                 (int)(t1 - t0), k);
+  EwW tot;
+  ew_block_excl<EwW, BLOCK>(s, wtot, &tot);
+  if (threadIdx.x == 0) tile_w[blockIdx.x] = tot;
+}
+
+// In-place exclusive scan of the tile summaries, 1024 per iteration with the
+// running carry held by every thread.  Both recurrences start from the zero
+// state, so afterwards tile_w[t].q / .cnt are tile t's entry W / nobs and
+// tile_m[t].b its entry mean.
+template <typename S>
+__global__ void __launch_bounds__(1024) k_ewm_scan_tiles(
+    S* __restrict__ tiles, int64_t ntiles) {
+  __shared__ S wtot[1024 / 64];
+  S carry = S::ident();
+  for (int64_t base = 0; base < ntiles; base += 1024) {
+    const int64_t i = base + threadIdx.x;
+    const S v = (i < ntiles) ? tiles[i] : S::ident();
+    S tot;
+    const S ex = ew_block_excl<S, 1024>(v, wtot, &tot);
+    if (i < ntiles) tiles[i] = S::then(carry, ex);
+    carry = S::then(carry, tot);
+  }
+}
+
+template <typename T, bool HEADS>
+__global__ void __launch_bounds__(BLOCK) k_ewm_m_tiles(
+    const T* __restrict__ in, const int64_t* __restrict__ heads, int64_t n,
+    EwPar k, const EwW* __restrict__ tile_w, EwM* __restrict__ tile_m) {
+  const int64_t t0 = (int64_t)blockIdx.x * FILT_TILE;
+  const int64_t t1 = min(t0 + (int64_t)FILT_TILE, n);
+  __shared__ double sv[EW_STAGE];
+  __shared__ unsigned char sf[HEADS ? FILT_TILE : 1];
+  __shared__ EwW wtot[BLOCK / 64];
+  __shared__ EwM mtot[BLOCK / 64];
+  ew_stage<T, HEADS>(in, heads, t0, t1, sv, sf);
+  const int s0 = threadIdx.x * EW_PER;
+  const int lim = (int)(t1 - t0);
+  EwW wt;
+  const EwW we = ew_block_excl<EwW, BLOCK>(
+      ew_w_fold<HEADS>(sv, sf, s0, lim, k), wtot, &wt);
+  const EwW entry = tile_w[blockIdx.x];
+  double W = we.p * entry.q + we.q;
+  long long nobs = we.keep ? entry.cnt + we.cnt : we.cnt;
+  EwM m = EwM::ident();
+#pragma unroll
+  for (int j = 0; j < EW_PER; ++j) {
+    if (s0 + j < lim)
+      m = EwM::then(m, ew_row(sv[ew_slot(s0 + j)], HEADS && sf[s0 + j], W,
+                              nobs, k));
+  }
+  EwM tot;
+  ew_block_excl<EwM, BLOCK>(m, mtot, &tot);
+  if (threadIdx.x == 0) tile_m[blockIdx.x] = tot;
+}
+
+template <typename T, bool HEADS>
+__global__ void __launch_bounds__(BLOCK) k_ewm_apply(
+    const T* __restrict__ in, const int64_t* __restrict__ heads, int64_t n,
+    EwPar k, const EwW* __restrict__ tile_w, const EwM* __restrict__ tile_m,
+    double* __restrict__ out) {
+  const int64_t t0 = (int64_t)blockIdx.x * FILT_TILE;
+  const int64_t t1 = min(t0 + (int64_t)FILT_TILE, n);
+  __shared__ double sv[EW_STAGE];
+  __shared__ unsigned char sf[HEADS ? FILT_TILE : 1];
+  __shared__ EwW wtot[BLOCK / 64];
+  __shared__ EwM mtot[BLOCK / 64];
+  ew_stage<T, HEADS>(in, heads, t0, t1, sv, sf);
+  const int s0 = threadIdx.x * EW_PER;
+  const int lim = (int)(t1 - t0);
+  EwW wt;
+  const EwW we = ew_block_excl<EwW, BLOCK>(
+      ew_w_fold<HEADS>(sv, sf, s0, lim, k), wtot, &wt);
+  const EwW entry = tile_w[blockIdx.x];
+  double W = we.p * entry.q + we.q;
+  const long long nobs0 = we.keep ? entry.cnt + we.cnt : we.cnt;
+  long long nobs = nobs0;
+  // inclusive mean map of the thread's run up to each row, in registers
+  double la[EW_PER], lb[EW_PER];
+  EwM m = EwM::ident();
+#pragma unroll
+  for (int j = 0; j < EW_PER; ++j) {
+    if (s0 + j < lim)
+      m = EwM::then(m, ew_row(sv[ew_slot(s0 + j)], HEADS && sf[s0 + j], W,
+                              nobs, k));
+    la[j] = m.a;
+    lb[j] = m.b;
+  }
+  EwM mt;
+  const EwM me = ew_block_excl<EwM, BLOCK>(m, mtot, &mt);
+  const double M0 = me.a * tile_m[blockIdx.x].b + me.b;
+  // each thread rewrites only its own run's slots: NaN rows are still
+  // readable as NaN until their turn, so nobs is recounted from LDS
+  nobs = nobs0;
+#pragma unroll
+  for (int j = 0; j < EW_PER; ++j) {
+    if (s0 + j < lim) {
+      const double x = sv[ew_slot(s0 + j)];
+      if (HEADS && sf[s0 + j]) nobs = 0;
+      nobs += (x == x);
+      sv[ew_slot(s0 + j)] = (nobs >= k.thresh) ? la[j] * M0 + lb[j]
+                                               : __builtin_nan("");
+    }
+  }
+  __syncthreads();
+  for (int j = 0; j < EW_PER; ++j) {
+    const int64_t i = t0 + (int64_t)j * BLOCK + threadIdx.x;
+    if (i < t1) out[i] = sv[ew_slot((int)(i - t0))];
+  }
+}
+
 }  // namespace
 
 struct hf_join {
@@ -3906,6 +4169,82 @@ int hf_seg_cumsum(const hf_col* col, const hf_col* heads, int agg_op,
   }();
   if (d_tf) dev_free(d_tf, g.stream);
   if (d_tv) dev_free(d_tv, g.stream);
+  if (rc != HF_OK) { hf_col_free(*out); *out = nullptr; }
+  return rc;
+}
+
+int hf_ewm_mean(const hf_col* col, const hf_col* heads, double alpha,
+                int adjust, int ignore_na, int64_t min_periods,
+                hf_col** out) {
+  HF_NEED_INIT("hf_ewm_mean");
+  if (!col || !out) return set_err(HF_ERR_ARG, "hf_ewm_mean", "null");
+  if (!(alpha > 0.0 && alpha <= 1.0))
+    return set_err(HF_ERR_ARG, "hf_ewm_mean", "alpha must be in (0, 1]");
+  if (min_periods < 0)
+    return set_err(HF_ERR_ARG, "hf_ewm_mean", "min_periods must be >= 0");
+  if (col->dtype != HF_FLOAT64 && col->dtype != HF_INT64)
+    return set_err(HF_ERR_ARG, "hf_ewm_mean", "col must be f64 or i64");
+  if (heads && (heads->dtype != HF_INT64 || heads->len != col->len))
+    return set_err(HF_ERR_ARG, "hf_ewm_mean",
+                   "heads must be an int64 0/1 column of the same length");
+  const int64_t n = col->len;
+  int rc = hf_col_alloc(n, HF_FLOAT64, out);
+  if (rc != HF_OK) return rc;
+  if (n == 0) return HF_OK;
+  const int64_t ntiles = (n + FILT_TILE - 1) / FILT_TILE;
+  EwPar k;
+  k.d = 1.0 - alpha;
+  k.nw = adjust ? 1.0 : alpha;
+  k.pval = adjust ? k.d : 0.0;
+  k.pnan = ignore_na ? 1.0 : k.d;
+  k.thresh = min_periods > 1 ? min_periods : 1;
+  void* d_tw = nullptr;
+  void* d_tm = nullptr;
+  rc = [&]() -> int {
+    HF_HIP("hf_ewm_mean",
+           dev_alloc(&d_tw, ntiles * (int64_t)sizeof(EwW), g.stream));
+    HF_HIP("hf_ewm_mean",
+           dev_alloc(&d_tm, ntiles * (int64_t)sizeof(EwM), g.stream));
+    auto run = [&](auto tTag, auto hTag) -> int {
+      using T = decltype(tTag);
+      constexpr bool H = decltype(hTag)::value;
+      const T* in = (const T*)col->dptr;
+      const int64_t* hd = H ? (const int64_t*)heads->dptr : nullptr;
+      const dim3 grid((uint32_t)ntiles);
+      int r2 = timed_launch("ewm_w_tiles", [&] {
+        hipLaunchKernelGGL((k_ewm_w_tiles<T, H>), grid, dim3(BLOCK), 0,
+                           g.stream, in, hd, n, k, (EwW*)d_tw);
+      });
+      if (r2 != HF_OK) return r2;
+      r2 = timed_launch("ewm_w_scan", [&] {
+        hipLaunchKernelGGL((k_ewm_scan_tiles<EwW>), dim3(1), dim3(1024), 0,
+                           g.stream, (EwW*)d_tw, ntiles);
+      });
+      if (r2 != HF_OK) return r2;
+      r2 = timed_launch("ewm_m_tiles", [&] {
+        hipLaunchKernelGGL((k_ewm_m_tiles<T, H>), grid, dim3(BLOCK), 0,
+                           g.stream, in, hd, n, k, (const EwW*)d_tw,
+                           (EwM*)d_tm);
+      });
+      if (r2 != HF_OK) return r2;
+      r2 = timed_launch("ewm_m_scan", [&] {
+        hipLaunchKernelGGL((k_ewm_scan_tiles<EwM>), dim3(1), dim3(1024), 0,
+                           g.stream, (EwM*)d_tm, ntiles);
+      });
+      if (r2 != HF_OK) return r2;
+      return timed_launch("ewm_apply", [&] {
+        hipLaunchKernelGGL((k_ewm_apply<T, H>), grid, dim3(BLOCK), 0,
+                           g.stream, in, hd, n, k, (const EwW*)d_tw,
+                           (const EwM*)d_tm, (double*)(*out)->dptr);
+      });
+    };
+    return with_bool(heads != nullptr, [&](auto hTag) -> int {
+      return (col->dtype == HF_FLOAT64) ? run(double{}, hTag)
+                                        : run(int64_t{}, hTag);
+    });
+  }();
+  if (d_tm) dev_free(d_tm, g.stream);
+  if (d_tw) dev_free(d_tw, g.stream);
   if (rc != HF_OK) { hf_col_free(*out); *out = nullptr; }
   return rc;
 }

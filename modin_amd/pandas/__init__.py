@@ -439,6 +439,16 @@ class _HipPandasBase:
         """pandas expanding(min_periods); .sum/.mean/.count/.min/.max."""
         return Expanding(self, min_periods)
 
+    def ewm(self, com=None, span=None, halflife=None, alpha=None,
+            min_periods=0, adjust: bool = True, ignore_na: bool = False,
+            axis=0, times=None, method: str = "single"):
+        """pandas ewm(com | span | halflife | alpha, min_periods, adjust,
+        ignore_na); .mean() is the one aggregation built."""
+        return ExponentialMovingWindow(
+            self, com=com, span=span, halflife=halflife, alpha=alpha,
+            min_periods=min_periods, adjust=adjust, ignore_na=ignore_na,
+            axis=axis, times=times, method=method)
+
     def ffill(self):
         """pandas ffill (forward fill down the rows)."""
         return self._rewrap(self._query_compiler.fillna_directional(
@@ -1909,6 +1919,13 @@ class DataFrameGroupBy:
                           else name)
         return DataFrame(query_compiler=qc)
 
+    def ewm(self, *args, **kwargs):
+        """pandas DataFrameGroupBy.ewm: per-group exponentially weighted
+        windows; the result rows come in group order under a
+        (keys..., original row label) MultiIndex."""
+        return ExponentialMovingWindow(self._df, *args, groupby=self,
+                                       **kwargs)
+
     def cumsum(self):
         return self._transform("cumsum")
 
@@ -2117,6 +2134,90 @@ def _window_var(obj, mk, ddof, sqrt_):
         v = v._rewrap(type(v._query_compiler).sqrt(
             v._query_compiler, 0.0))
     return v
+
+
+class ExponentialMovingWindow:
+    """pandas ExponentialMovingWindow (and its groupby form) for .mean().
+    The reference defaults every ewm to pandas (modin/pandas/base.py:1645,
+    modin/pandas/groupby.py:493); here mean() is one device recurrence
+    scan per column.  The decay is validated and reduced to alpha by
+    pandas' own rules (pandas.core.window.common.get_center_of_mass)."""
+
+    def __init__(self, obj, com=None, span=None, halflife=None, alpha=None,
+                 min_periods=0, adjust: bool = True, ignore_na: bool = False,
+                 axis=0, times=None, method: str = "single", groupby=None):
+        if times is not None:
+            raise lib.HfError("ewm(times=...) is not built")
+        if axis not in (0, "index"):
+            raise lib.HfError("ewm(axis=1) is not built")
+        if method != "single":
+            raise lib.HfError(f"ewm(method={method!r}) is not built")
+        if halflife is not None and not isinstance(
+                halflife, (int, float, np.integer, np.floating)):
+            raise lib.HfError("ewm: a timedelta halflife needs times=, "
+                              "which is not built")
+        if groupby is not None and not groupby._dropna:
+            raise lib.HfError("groupby(dropna=False).ewm is not built")
+        given = sum(a is not None for a in (com, span, halflife, alpha))
+        if given > 1:
+            raise ValueError("comass, span, halflife, and alpha are "
+                             "mutually exclusive")
+        if com is not None:
+            if com < 0:
+                raise ValueError("comass must satisfy: comass >= 0")
+        elif span is not None:
+            if span < 1:
+                raise ValueError("span must satisfy: span >= 1")
+            com = (span - 1) / 2
+        elif halflife is not None:
+            if halflife <= 0:
+                raise ValueError("halflife must satisfy: halflife > 0")
+            decay = 1 - np.exp(np.log(0.5) / halflife)
+            com = 1 / decay - 1
+        elif alpha is not None:
+            if alpha <= 0 or alpha > 1:
+                raise ValueError("alpha must satisfy: 0 < alpha <= 1")
+            com = (1 - alpha) / alpha
+        else:
+            raise ValueError("Must pass one of comass, span, halflife, or "
+                             "alpha")
+        self._obj = obj
+        self._groupby = groupby
+        self._alpha = 1.0 / (1.0 + float(com))
+        self._min_periods = max(int(min_periods or 0), 0)
+        self._adjust = bool(adjust)
+        self._ignore_na = bool(ignore_na)
+
+    def mean(self):
+        args = (self._alpha, self._adjust, self._ignore_na,
+                self._min_periods)
+        gb = self._groupby
+        if gb is None:
+            return self._obj._rewrap(
+                self._obj._query_compiler.ewm_mean(*args))
+        qc = self._obj._query_compiler.groupby_ewm_mean(gb._by, *args)
+        if gb._series_out:
+            return Series(query_compiler=qc,
+                          name=list(qc._modin_frame.columns)[0])
+        return DataFrame(query_compiler=qc)
+
+    def _not_built(self, what: str):
+        raise lib.HfError(f"ewm.{what} is not built (only ewm.mean is)")
+
+    def var(self, *args, **kwargs):
+        self._not_built("var")
+
+    def std(self, *args, **kwargs):
+        self._not_built("std")
+
+    def sum(self, *args, **kwargs):
+        self._not_built("sum")
+
+    def cov(self, *args, **kwargs):
+        self._not_built("cov")
+
+    def corr(self, *args, **kwargs):
+        self._not_built("corr")
 
 
 class Expanding:

@@ -739,6 +739,18 @@ class HipQueryCompiler:
         return self.__constructor__(self._modin_frame.expanding_agg(
             min_periods, op))
 
+    def ewm_mean(self, alpha: float, adjust: bool = True,
+                 ignore_na: bool = False,
+                 min_periods: int = 0) -> "HipQueryCompiler":
+        return self.__constructor__(self._modin_frame.ewm_mean(
+            alpha, adjust, ignore_na, min_periods))
+
+    def groupby_ewm_mean(self, by, alpha: float, adjust: bool = True,
+                         ignore_na: bool = False,
+                         min_periods: int = 0) -> "HipQueryCompiler":
+        return self.__constructor__(self._modin_frame.groupby_ewm_mean(
+            by, alpha, adjust, ignore_na, min_periods))
+
     def fillna_dict(self, values: dict) -> "HipQueryCompiler":
         """pandas fillna({column: scalar}): per-column fill values;
         unlisted columns pass through."""
