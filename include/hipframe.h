@@ -81,6 +81,11 @@ uintptr_t hf_col_dptr(const hf_col* col);  /* raw device ptr (RCCL/torch
 int  hf_alloc_raw(int64_t bytes, uintptr_t* dptr);
 int  hf_free_raw(uintptr_t dptr);
 int  hf_memset_raw(uintptr_t dptr, int value, int64_t bytes);
+/* Device blocks currently handed out by the module's allocator (columns and
+ * their caches, raw buffers, join/filter handles, temporaries of a running
+ * call) and not yet given back.  A call that fails, or whose results have all
+ * been freed, leaves this where it was: the ownership tests assert that. */
+int  hf_dev_live(int64_t* blocks);
 
 /* ---- Map: elementwise scalar ops ----
  * Device form of the Map operator template

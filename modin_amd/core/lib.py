@@ -95,7 +95,8 @@ def load() -> ct.CDLL:
             "hf_alloc_raw": (ct.c_int, [ct.c_int64, ct.POINTER(ct.c_size_t)]),
             "hf_free_raw": (ct.c_int, [ct.c_size_t]),
             "hf_memset_raw": (ct.c_int, [ct.c_size_t, ct.c_int, ct.c_int64]),
-            "hf_map_scalar": (ct.c_int, [ct.c_int, ct.c_void_p, ct.c_double,
+            "hf_dev_live": (ct.c_int, [ct.POINTER(ct.c_int64)]),
+            "hf_map_scalar":(ct.c_int, [ct.c_int, ct.c_void_p, ct.c_double,
                                          ct.POINTER(ct.c_void_p)]),
             "hf_map_scalar_i64": (ct.c_int, [ct.c_int, ct.c_void_p, ct.c_int64,
                                              ct.POINTER(ct.c_void_p)]),
@@ -211,7 +212,8 @@ def exported_symbols():
         "hf_init", "hf_shutdown", "hf_device_count", "hf_last_error", "hf_sync",
         "hf_put", "hf_get", "hf_col_alloc", "hf_col_free", "hf_col_len",
         "hf_col_dtype", "hf_col_dptr", "hf_alloc_raw", "hf_free_raw",
-        "hf_memset_raw", "hf_map_scalar", "hf_map_scalar_i64", "hf_binary",
+        "hf_memset_raw", "hf_dev_live", "hf_map_scalar", "hf_map_scalar_i64",
+        "hf_binary",
         "hf_reduce", "hf_groupby_accum", "hf_group_moments",
         "hf_groupby_compact", "hf_fill_f64",
         "hf_fixup_empty", "hf_sort_perm", "hf_fill_i64",
@@ -403,6 +405,15 @@ def free_raw(dptr: int) -> None:
 
 def memset_raw(dptr: int, value: int, nbytes: int) -> None:
     _check(load().hf_memset_raw(dptr, value, nbytes), "hf_memset_raw")
+
+
+def dev_live() -> int:
+    """Device blocks the engine's allocator has handed out and not got back
+    (columns, raw buffers, join/filter handles)."""
+    ensure_ready()
+    n = ct.c_int64(0)
+    _check(load().hf_dev_live(ct.byref(n)), "hf_dev_live")
+    return n.value
 
 
 AGG_SUM, AGG_MIN, AGG_MAX, AGG_PROD = range(4)

@@ -124,6 +124,8 @@ constexpr int64_t SCRATCH_JOIN_HIST_ERR = 144;
 constexpr int64_t SCRATCH_JOIN_FIXUP_ERR = 152;
 constexpr int64_t SCRATCH_HASH_FULL = 160;
 constexpr int64_t SCRATCH_GM_ERR = 168;
+template <typename T = unsigned long long>
+T* scratch_at(int64_t off) { return (T*)((char*)g.d_scratch + off); }
 
 int set_err(int code, const char* where, const char* what) {
   g_err = std::string(where) + ": " + what;
@@ -195,23 +197,37 @@ int timed_launch(const char* name, F&& launch) {
 // std::integral_constant and the caller reads decltype(tag)::value.  Callers
 // validate agg_op / nvals first.  Only the combinations a caller actually
 // nests are instantiated.
+template <int V>
+using int_tag = std::integral_constant<int, V>;
 template <typename F>
 int with_bool(bool b, F&& f) {
   return b ? f(std::true_type{}) : f(std::false_type{});
 }
 template <typename F>
 int with_aop(int agg_op, F&& f) {
-  return agg_op == HF_AGG_SUM   ? f(std::integral_constant<int, HF_AGG_SUM>{})
-         : agg_op == HF_AGG_MIN ? f(std::integral_constant<int, HF_AGG_MIN>{})
-                                : f(std::integral_constant<int, HF_AGG_MAX>{});
+  return agg_op == HF_AGG_SUM   ? f(int_tag<HF_AGG_SUM>{})
+         : agg_op == HF_AGG_MIN ? f(int_tag<HF_AGG_MIN>{})
+                                : f(int_tag<HF_AGG_MAX>{});
 }
 template <int MAX, int N = 0, typename F>
 int with_nvals(int nv, F&& f) {  // nv in [0, MAX]
-  if (nv == N) return f(std::integral_constant<int, N>{});
+  if (nv == N) return f(int_tag<N>{});
   if constexpr (N < MAX)
     return with_nvals<MAX, N + 1>(nv, std::forward<F>(f));
   else
-    return set_err(HF_ERR_ARG, "groupby", "nvals out of range");
+    return set_err(HF_ERR_ARG, "with_nvals", "column count out of range");
+}
+// The scan ops are with_aop's plus PROD.  Kept apart from with_aop, whose
+// groupby callers would otherwise instantiate PROD kernels they never launch.
+template <typename F>
+int with_scan_op(int agg_op, F&& f) {
+  return agg_op == HF_AGG_PROD ? f(int_tag<HF_AGG_PROD>{})
+                               : with_aop(agg_op, std::forward<F>(f));
+}
+// column dtype -> a value of its element type (double{} or int64_t{})
+template <typename F>
+int with_dtype(int dtype, F&& f) {
+  return dtype == HF_FLOAT64 ? f(double{}) : f(int64_t{});
 }
 
 constexpr int BLOCK = 256;
@@ -281,12 +297,19 @@ struct DevCache {
   }
 };
 DevCache g_cache;
+// blocks handed out by dev_alloc and not yet given back through dev_free
+// (hf_dev_live): the balance the ownership tests assert
+int64_t g_dev_live = 0;
 
 inline hipError_t dev_alloc(void** p, int64_t bytes, hipStream_t s) {
-  if (sync_alloc()) { hipStreamSynchronize(s); return hipMalloc(p, bytes); }
-  return g_cache.alloc(p, bytes);
+  if (sync_alloc()) hipStreamSynchronize(s);
+  const hipError_t e = sync_alloc() ? hipMalloc(p, bytes)
+                                    : g_cache.alloc(p, bytes);
+  if (e == hipSuccess) ++g_dev_live;
+  return e;
 }
 inline hipError_t dev_free(void* p, hipStream_t s) {
+  --g_dev_live;
   if (sync_alloc()) { hipStreamSynchronize(s); return hipFree(p); }
   g_cache.free(p);
   return hipSuccess;
@@ -308,6 +331,15 @@ class DevBuf {
     return e;
   }
   void* release() { void* p = p_; p_ = nullptr; return p; }
+  // allocate straight into a field of a handle whose owner frees it
+  // (hf_join_free, hf_filter_plan_free); null on failure
+  template <typename T>
+  static hipError_t alloc_into(T*& field, int64_t bytes) {
+    DevBuf b;
+    const hipError_t e = b.alloc(bytes);
+    field = static_cast<T*>(b.release());
+    return e;
+  }
   template <typename T>
   T* as() const { return static_cast<T*>(p_); }
 
@@ -321,6 +353,53 @@ void drop_dev(void*& p) {
   if (p && g.inited) (void)dev_free(p, g.stream);
   p = nullptr;
 }
+
+// An hf_col that is allocated but not yet the caller's: freed on scope exit
+// unless commit() hands it out.  Entry points commit their outputs as the
+// last thing before returning HF_OK, so a failed call leaves no column behind
+// and no pointer to one in the caller's slot.  Move-only.
+class ColOut {
+ public:
+  ColOut() = default;
+  ColOut(ColOut&& o) noexcept : c_(o.c_) { o.c_ = nullptr; }
+  ColOut(const ColOut&) = delete;
+  ColOut& operator=(const ColOut&) = delete;
+  ~ColOut() { hf_col_free(c_); }
+  int alloc(int64_t len, int dtype) {  // call once per holder
+    return hf_col_alloc(len, dtype, &c_);
+  }
+  hf_col** slot() { return &c_; }  // to receive another entry point's output
+  hf_col* get() const { return c_; }
+  template <typename T>
+  T* data() const { return static_cast<T*>(c_->dptr); }
+  void commit(hf_col** out) { *out = c_; c_ = nullptr; }
+  // tail of an entry point whose last step returned rc: commit on success,
+  // leave a null in the caller's slot otherwise
+  int commit_if(int rc, hf_col** out) {
+    if (rc == HF_OK) commit(out); else *out = nullptr;
+    return rc;
+  }
+
+ private:
+  hf_col* c_ = nullptr;
+};
+
+// The output triple of the groupby entry points: keys, one sum column per
+// value and, when wanted, one count column per value; committed together.
+struct GroupOut {
+  ColOut keys;
+  std::vector<ColOut> sums, cnts;
+  GroupOut(int nvals, bool counts) : sums(nvals), cnts(counts ? nvals : 0) {}
+  void commit(hf_col** out_keys, hf_col** out_sums, hf_col** out_counts) {
+    keys.commit(out_keys);
+    for (size_t c = 0; c < sums.size(); ++c) sums[c].commit(&out_sums[c]);
+    for (size_t c = 0; c < cnts.size(); ++c) cnts[c].commit(&out_counts[c]);
+  }
+};
+
+// owners for the two handle types while an entry point builds or borrows one
+using JoinOwner = std::unique_ptr<hf_join, int (*)(hf_join*)>;
+using PlanOwner = std::unique_ptr<hf_filterplan, int (*)(hf_filterplan*)>;
 }  // namespace
 
 void GbKeyCache::drop_plan() {
@@ -2943,12 +3022,6 @@ struct hf_join {
   int dtypes[GB_MAX_VALS];     // per right column
 };
 
-// forward decls used by the map launch helpers (defined in the C ABI below)
-extern "C" int hf_col_alloc(int64_t len, int dtype, hf_col** out);
-extern "C" int hf_col_free(hf_col* col);
-extern "C" int hf_map_scalar_i64(int op, const hf_col* in, int64_t scalar,
-                                 hf_col** out);
-
 namespace {
 template <int OP>
 int launch_map_f64(const hf_col* in, double s, hf_col* out) {
@@ -2995,6 +3068,7 @@ int hf_shutdown(void) {
   if (!g.inited) return HF_OK;
   hipStreamSynchronize(g.stream);
   g_cache.trim();
+  g_dev_live = 0;  // blocks still out are only forgotten from here on
   for (auto& p : g.pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
   g.pending.clear();
   g.stats.clear();
@@ -3037,11 +3111,14 @@ int hf_col_alloc(int64_t len, int dtype, hf_col** out) {
 
 int hf_put(const void* host, int64_t len, int dtype, hf_col** out) {
   HF_NEED_INIT("hf_put");
-  int rc = hf_col_alloc(len, dtype, out);
+  if (!out) return set_err(HF_ERR_ARG, "hf_put", "null");
+  ColOut col;
+  int rc = col.alloc(len, dtype);
   if (rc != HF_OK) return rc;
   if (len > 0)
-    HF_HIP("hf_put", hipMemcpyAsync((*out)->dptr, host, len * dtype_size(dtype),
+    HF_HIP("hf_put", hipMemcpyAsync(col.get()->dptr, host, len * dtype_size(dtype),
                                     hipMemcpyHostToDevice, g.stream));
+  col.commit(out);
   return HF_OK;
 }
 
@@ -3079,6 +3156,11 @@ int hf_free_raw(uintptr_t dptr) {
   HF_HIP("hf_free_raw", dev_free((void*)dptr, g.stream));
   return HF_OK;
 }
+int hf_dev_live(int64_t* blocks) {
+  if (!blocks) return set_err(HF_ERR_ARG, "hf_dev_live", "null");
+  *blocks = g_dev_live;
+  return HF_OK;
+}
 int hf_memset_raw(uintptr_t dptr, int value, int64_t bytes) {
   HF_NEED_INIT("hf_memset_raw");
   HF_HIP("hf_memset_raw", hipMemsetAsync((void*)dptr, value, bytes, g.stream));
@@ -3090,52 +3172,52 @@ int hf_memset_raw(uintptr_t dptr, int value, int64_t bytes) {
 int hf_map_scalar(int op, const hf_col* in, double scalar, hf_col** out) {
   HF_NEED_INIT("hf_map_scalar");
   if (!in || !out) return set_err(HF_ERR_ARG, "hf_map_scalar", "null");
+  ColOut o;
   if (op == HF_MAP_CAST_F64) {
     if (in->dtype != HF_INT64)
       return set_err(HF_ERR_ARG, "hf_map_scalar", "cast_f64 needs int64 input");
-    int rc = hf_col_alloc(in->len, HF_FLOAT64, out);
+    int rc = o.alloc(in->len, HF_FLOAT64);
     if (rc != HF_OK) return rc;
-    return timed_launch("cast_i64_f64", [&] {
+    rc = timed_launch("cast_i64_f64", [&] {
       hipLaunchKernelGGL(k_cast_i64_f64, dim3(grid_for(in->len)), dim3(BLOCK), 0,
-                         g.stream, (const int64_t*)in->dptr, (double*)(*out)->dptr,
+                         g.stream, (const int64_t*)in->dptr, o.data<double>(),
                          in->len);
     });
+    return o.commit_if(rc, out);
   }
   if (op == HF_MAP_CAST_I64) {
     if (in->dtype != HF_FLOAT64)
       return set_err(HF_ERR_ARG, "hf_map_scalar", "cast_i64 needs f64 input");
-    int rc = hf_col_alloc(in->len, HF_INT64, out);
+    int rc = o.alloc(in->len, HF_INT64);
     if (rc != HF_OK) return rc;
-    return timed_launch("cast_f64_i64", [&] {
+    rc = timed_launch("cast_f64_i64", [&] {
       hipLaunchKernelGGL(k_cast_f64_i64, dim3(grid_for(in->len)), dim3(BLOCK), 0,
-                         g.stream, (const double*)in->dptr,
-                         (int64_t*)(*out)->dptr, in->len);
+                         g.stream, (const double*)in->dptr, o.data<int64_t>(),
+                         in->len);
     });
+    return o.commit_if(rc, out);
   }
   if (in->dtype == HF_INT64) return hf_map_scalar_i64(op, in, (int64_t)scalar, out);
-  int rc = hf_col_alloc(in->len, HF_FLOAT64, out);
+  int rc = o.alloc(in->len, HF_FLOAT64);
   if (rc != HF_OK) return rc;
   switch (op) {
-    case HF_MAP_ADD:    rc = launch_map_f64<HF_MAP_ADD>(in, scalar, *out); break;
-    case HF_MAP_SUB:    rc = launch_map_f64<HF_MAP_SUB>(in, scalar, *out); break;
-    case HF_MAP_RSUB:   rc = launch_map_f64<HF_MAP_RSUB>(in, scalar, *out); break;
-    case HF_MAP_MUL:    rc = launch_map_f64<HF_MAP_MUL>(in, scalar, *out); break;
-    case HF_MAP_DIV:    rc = launch_map_f64<HF_MAP_DIV>(in, scalar, *out); break;
-    case HF_MAP_RDIV:   rc = launch_map_f64<HF_MAP_RDIV>(in, scalar, *out); break;
-    case HF_MAP_FILLNA: rc = launch_map_f64<HF_MAP_FILLNA>(in, scalar, *out); break;
-    case HF_MAP_ABS:    rc = launch_map_f64<HF_MAP_ABS>(in, scalar, *out); break;
-    case HF_MAP_NEG:    rc = launch_map_f64<HF_MAP_NEG>(in, scalar, *out); break;
-    case HF_MAP_SQRT:   rc = launch_map_f64<HF_MAP_SQRT>(in, scalar, *out); break;
-    case HF_MAP_MIN:    rc = launch_map_f64<HF_MAP_MIN>(in, scalar, *out); break;
-    case HF_MAP_MAX:    rc = launch_map_f64<HF_MAP_MAX>(in, scalar, *out); break;
-    case HF_MAP_ROUND:  rc = launch_map_f64<HF_MAP_ROUND>(in, scalar, *out); break;
+    case HF_MAP_ADD:    rc = launch_map_f64<HF_MAP_ADD>(in, scalar, o.get()); break;
+    case HF_MAP_SUB:    rc = launch_map_f64<HF_MAP_SUB>(in, scalar, o.get()); break;
+    case HF_MAP_RSUB:   rc = launch_map_f64<HF_MAP_RSUB>(in, scalar, o.get()); break;
+    case HF_MAP_MUL:    rc = launch_map_f64<HF_MAP_MUL>(in, scalar, o.get()); break;
+    case HF_MAP_DIV:    rc = launch_map_f64<HF_MAP_DIV>(in, scalar, o.get()); break;
+    case HF_MAP_RDIV:   rc = launch_map_f64<HF_MAP_RDIV>(in, scalar, o.get()); break;
+    case HF_MAP_FILLNA: rc = launch_map_f64<HF_MAP_FILLNA>(in, scalar, o.get()); break;
+    case HF_MAP_ABS:    rc = launch_map_f64<HF_MAP_ABS>(in, scalar, o.get()); break;
+    case HF_MAP_NEG:    rc = launch_map_f64<HF_MAP_NEG>(in, scalar, o.get()); break;
+    case HF_MAP_SQRT:   rc = launch_map_f64<HF_MAP_SQRT>(in, scalar, o.get()); break;
+    case HF_MAP_MIN:    rc = launch_map_f64<HF_MAP_MIN>(in, scalar, o.get()); break;
+    case HF_MAP_MAX:    rc = launch_map_f64<HF_MAP_MAX>(in, scalar, o.get()); break;
+    case HF_MAP_ROUND:  rc = launch_map_f64<HF_MAP_ROUND>(in, scalar, o.get()); break;
     default:
-      hf_col_free(*out);
-      *out = nullptr;
-      return set_err(HF_ERR_UNSUPPORTED, "hf_map_scalar", "unknown op");
+      rc = set_err(HF_ERR_UNSUPPORTED, "hf_map_scalar", "unknown op");
   }
-  if (rc != HF_OK) { hf_col_free(*out); *out = nullptr; }
-  return rc;
+  return o.commit_if(rc, out);
 }
 
 int hf_map_scalar_i64(int op, const hf_col* in, int64_t scalar, hf_col** out) {
@@ -3143,41 +3225,32 @@ int hf_map_scalar_i64(int op, const hf_col* in, int64_t scalar, hf_col** out) {
   if (!in || !out) return set_err(HF_ERR_ARG, "hf_map_scalar_i64", "null");
   if (in->dtype != HF_INT64)
     return set_err(HF_ERR_ARG, "hf_map_scalar_i64", "int64 column required");
-  int rc = hf_col_alloc(in->len, HF_INT64, out);
+  ColOut o;
+  int rc = o.alloc(in->len, HF_INT64);
   if (rc != HF_OK) return rc;
   switch (op) {
-    case HF_MAP_ADD:  rc = launch_map_i64<HF_MAP_ADD>(in, scalar, *out); break;
-    case HF_MAP_SUB:  rc = launch_map_i64<HF_MAP_SUB>(in, scalar, *out); break;
-    case HF_MAP_RSUB: rc = launch_map_i64<HF_MAP_RSUB>(in, scalar, *out); break;
-    case HF_MAP_MUL:  rc = launch_map_i64<HF_MAP_MUL>(in, scalar, *out); break;
-    case HF_MAP_ABS:  rc = launch_map_i64<HF_MAP_ABS>(in, scalar, *out); break;
-    case HF_MAP_NEG:  rc = launch_map_i64<HF_MAP_NEG>(in, scalar, *out); break;
-    case HF_MAP_MIN:  rc = launch_map_i64<HF_MAP_MIN>(in, scalar, *out); break;
-    case HF_MAP_MAX:  rc = launch_map_i64<HF_MAP_MAX>(in, scalar, *out); break;
+    case HF_MAP_ADD:  rc = launch_map_i64<HF_MAP_ADD>(in, scalar, o.get()); break;
+    case HF_MAP_SUB:  rc = launch_map_i64<HF_MAP_SUB>(in, scalar, o.get()); break;
+    case HF_MAP_RSUB: rc = launch_map_i64<HF_MAP_RSUB>(in, scalar, o.get()); break;
+    case HF_MAP_MUL:  rc = launch_map_i64<HF_MAP_MUL>(in, scalar, o.get()); break;
+    case HF_MAP_ABS:  rc = launch_map_i64<HF_MAP_ABS>(in, scalar, o.get()); break;
+    case HF_MAP_NEG:  rc = launch_map_i64<HF_MAP_NEG>(in, scalar, o.get()); break;
+    case HF_MAP_MIN:  rc = launch_map_i64<HF_MAP_MIN>(in, scalar, o.get()); break;
+    case HF_MAP_MAX:  rc = launch_map_i64<HF_MAP_MAX>(in, scalar, o.get()); break;
     case HF_MAP_IDIV:
-      if (scalar == 0) {
-        hf_col_free(*out);
-        *out = nullptr;
-        return set_err(HF_ERR_ARG, "hf_map_scalar_i64", "floordiv by zero");
-      }
-      rc = launch_map_i64<HF_MAP_IDIV>(in, scalar, *out);
+      rc = scalar == 0
+               ? set_err(HF_ERR_ARG, "hf_map_scalar_i64", "floordiv by zero")
+               : launch_map_i64<HF_MAP_IDIV>(in, scalar, o.get());
       break;
     case HF_MAP_IMOD:
-      if (scalar == 0) {
-        hf_col_free(*out);
-        *out = nullptr;
-        return set_err(HF_ERR_ARG, "hf_map_scalar_i64", "mod by zero");
-      }
-      rc = launch_map_i64<HF_MAP_IMOD>(in, scalar, *out);
+      rc = scalar == 0 ? set_err(HF_ERR_ARG, "hf_map_scalar_i64", "mod by zero")
+                       : launch_map_i64<HF_MAP_IMOD>(in, scalar, o.get());
       break;
     default:
-      hf_col_free(*out);
-      *out = nullptr;
-      return set_err(HF_ERR_UNSUPPORTED, "hf_map_scalar_i64",
-                     "op not defined for int64 (div promotes via cast_f64)");
+      rc = set_err(HF_ERR_UNSUPPORTED, "hf_map_scalar_i64",
+                   "op not defined for int64 (div promotes via cast_f64)");
   }
-  if (rc != HF_OK) { hf_col_free(*out); *out = nullptr; }
-  return rc;
+  return o.commit_if(rc, out);
 }
 
 // ---- binary ----
@@ -3192,7 +3265,8 @@ int hf_binary(int op, const hf_col* a, const hf_col* b, hf_col** out) {
   const bool f64 = a->dtype == HF_FLOAT64;
   if (!f64 && op == HF_BIN_DIV)
     return set_err(HF_ERR_UNSUPPORTED, "hf_binary", "int64 div promotes via cast_f64");
-  int rc = hf_col_alloc(a->len, a->dtype, out);
+  ColOut o;
+  int rc = o.alloc(a->len, a->dtype);
   if (rc != HF_OK) return rc;
   const int64_t n = a->len;
   // dispatch with typed wrappers
@@ -3201,7 +3275,7 @@ int hf_binary(int op, const hf_col* a, const hf_col* b, hf_col** out) {
     return timed_launch("bin_f64", [&] {
       hipLaunchKernelGGL((k_bin<O, double, double2>), dim3(grid_for((n >> 1) + 1)),
                          dim3(BLOCK), 0, g.stream, (const double*)a->dptr,
-                         (const double*)b->dptr, (double*)(*out)->dptr, n);
+                         (const double*)b->dptr, o.data<double>(), n);
     });
   };
   auto Li = [&](auto opTag) {
@@ -3209,28 +3283,20 @@ int hf_binary(int op, const hf_col* a, const hf_col* b, hf_col** out) {
     return timed_launch("bin_i64", [&] {
       hipLaunchKernelGGL((k_bin<O, int64_t, longlong2>), dim3(grid_for((n >> 1) + 1)),
                          dim3(BLOCK), 0, g.stream, (const int64_t*)a->dptr,
-                         (const int64_t*)b->dptr, (int64_t*)(*out)->dptr, n);
+                         (const int64_t*)b->dptr, o.data<int64_t>(), n);
     });
   };
   switch (op) {
-    case HF_BIN_ADD: rc = f64 ? Lf(std::integral_constant<int, HF_BIN_ADD>{})
-                              : Li(std::integral_constant<int, HF_BIN_ADD>{}); break;
-    case HF_BIN_SUB: rc = f64 ? Lf(std::integral_constant<int, HF_BIN_SUB>{})
-                              : Li(std::integral_constant<int, HF_BIN_SUB>{}); break;
-    case HF_BIN_MUL: rc = f64 ? Lf(std::integral_constant<int, HF_BIN_MUL>{})
-                              : Li(std::integral_constant<int, HF_BIN_MUL>{}); break;
-    case HF_BIN_DIV: rc = Lf(std::integral_constant<int, HF_BIN_DIV>{}); break;
-    case HF_BIN_MIN: rc = f64 ? Lf(std::integral_constant<int, HF_BIN_MIN>{})
-                              : Li(std::integral_constant<int, HF_BIN_MIN>{}); break;
-    case HF_BIN_MAX: rc = f64 ? Lf(std::integral_constant<int, HF_BIN_MAX>{})
-                              : Li(std::integral_constant<int, HF_BIN_MAX>{}); break;
+    case HF_BIN_ADD: rc = f64 ? Lf(int_tag<HF_BIN_ADD>{}) : Li(int_tag<HF_BIN_ADD>{}); break;
+    case HF_BIN_SUB: rc = f64 ? Lf(int_tag<HF_BIN_SUB>{}) : Li(int_tag<HF_BIN_SUB>{}); break;
+    case HF_BIN_MUL: rc = f64 ? Lf(int_tag<HF_BIN_MUL>{}) : Li(int_tag<HF_BIN_MUL>{}); break;
+    case HF_BIN_DIV: rc = Lf(int_tag<HF_BIN_DIV>{}); break;
+    case HF_BIN_MIN: rc = f64 ? Lf(int_tag<HF_BIN_MIN>{}) : Li(int_tag<HF_BIN_MIN>{}); break;
+    case HF_BIN_MAX: rc = f64 ? Lf(int_tag<HF_BIN_MAX>{}) : Li(int_tag<HF_BIN_MAX>{}); break;
     default:
-      hf_col_free(*out);
-      *out = nullptr;
-      return set_err(HF_ERR_UNSUPPORTED, "hf_binary", "unknown op");
+      rc = set_err(HF_ERR_UNSUPPORTED, "hf_binary", "unknown op");
   }
-  if (rc != HF_OK) { hf_col_free(*out); *out = nullptr; }
-  return rc;
+  return o.commit_if(rc, out);
 }
 
 // ---- reduce ----
@@ -3668,8 +3734,7 @@ int hf_groupby_accum(const hf_col* keys, const hf_col* const* vals, int nvals,
     ptrs.vals[c] = (const double*)vals[c]->dptr;
   }
   const int64_t n = keys->len;
-  unsigned long long* d_err =
-      (unsigned long long*)((char*)g.d_scratch + SCRATCH_GB_ERR);
+  unsigned long long* d_err = scratch_at(SCRATCH_GB_ERR);
   // path selection (DESIGN.md §GroupBy kernels): LDS-dense for small ranges,
   // radix partition for the north-star range, global atomics as the wide
   // fallback (slow but correct for any range below the slot cap)
@@ -3757,8 +3822,7 @@ int hf_group_moments(const hf_col* gid, const hf_col* val, uintptr_t centre,
                          g.stream, d_val, n, d_c, d_tab);
     });
   }
-  unsigned long long* d_err =
-      (unsigned long long*)((char*)g.d_scratch + SCRATCH_GM_ERR);
+  unsigned long long* d_err = scratch_at(SCRATCH_GM_ERR);
   HF_HIP("hf_group_moments", hipMemsetAsync(d_err, 0, 8, g.stream));
   const int64_t* d_gid = (const int64_t*)gid->dptr;
   int rc;
@@ -3799,15 +3863,14 @@ int hf_groupby_compact(uintptr_t sums, uintptr_t rowcnt, uintptr_t counts,
   const int64_t ntiles = (n_slots + COMPACT_TILE - 1) / COMPACT_TILE;
   // check the accumulate-phase error word
   unsigned long long h_err = 0;
-  unsigned long long* d_err =
-      (unsigned long long*)((char*)g.d_scratch + SCRATCH_GB_ERR);
+  unsigned long long* d_err = scratch_at(SCRATCH_GB_ERR);
   HF_HIP("hf_groupby_compact",
          hipMemcpyAsync(&h_err, d_err, 8, hipMemcpyDeviceToHost, g.stream));
   // tile counts
-  int64_t* d_tiles = nullptr;
-  HF_HIP("hf_groupby_compact",
-         dev_alloc((void**)&d_tiles, (ntiles + 1) * 8, g.stream));
-  int64_t* d_total = (int64_t*)((char*)g.d_scratch + SCRATCH_NGROUPS);
+  DevBuf tiles_buf;
+  HF_HIP("hf_groupby_compact", tiles_buf.alloc((ntiles + 1) * 8));
+  int64_t* d_tiles = tiles_buf.as<int64_t>();
+  int64_t* d_total = scratch_at<int64_t>(SCRATCH_NGROUPS);
   int rc = timed_launch("gb_compact_count", [&] {
     hipLaunchKernelGGL(k_compact_count, dim3((uint32_t)ntiles), dim3(BLOCK), 0,
                        g.stream, (const unsigned long long*)rowcnt, n_slots, d_tiles);
@@ -3823,7 +3886,6 @@ int hf_groupby_compact(uintptr_t sums, uintptr_t rowcnt, uintptr_t counts,
          hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, g.stream));
   HF_HIP("hf_groupby_compact", hipStreamSynchronize(g.stream));
   if (h_err != 0) {
-    dev_free(d_tiles, g.stream);
     char buf[128];
     snprintf(buf, sizeof buf,
              "%llu keys fell outside [key_min, key_min+n_slots) during accumulate",
@@ -3832,55 +3894,49 @@ int hf_groupby_compact(uintptr_t sums, uintptr_t rowcnt, uintptr_t counts,
     return set_err(HF_ERR_ARG, "hf_groupby_compact", buf);
   }
   // allocate outputs
-  rc = hf_col_alloc(total, HF_INT64, out_keys);
+  const bool want_counts = counts && out_counts;
+  GroupOut o(nvals, want_counts);
+  rc = o.keys.alloc(total, HF_INT64);
   if (rc != HF_OK) return rc;
   std::vector<double*> h_sum_ptrs(nvals ? nvals : 1);
   std::vector<int64_t*> h_cnt_ptrs(nvals ? nvals : 1);
   for (int c = 0; c < nvals; ++c) {
-    rc = hf_col_alloc(total, HF_FLOAT64, &out_sums[c]);
+    rc = o.sums[c].alloc(total, HF_FLOAT64);
     if (rc != HF_OK) return rc;
-    h_sum_ptrs[c] = (double*)out_sums[c]->dptr;
-    if (counts && out_counts) {
-      rc = hf_col_alloc(total, HF_INT64, &out_counts[c]);
+    h_sum_ptrs[c] = o.sums[c].data<double>();
+    if (want_counts) {
+      rc = o.cnts[c].alloc(total, HF_INT64);
       if (rc != HF_OK) return rc;
-      h_cnt_ptrs[c] = (int64_t*)out_counts[c]->dptr;
+      h_cnt_ptrs[c] = o.cnts[c].data<int64_t>();
     }
   }
   // ship the per-column output pointer arrays to the device
-  double** d_sum_ptrs = nullptr;
-  int64_t** d_cnt_ptrs = nullptr;
+  DevBuf sum_ptrs_buf, cnt_ptrs_buf;
   HF_HIP("hf_groupby_compact",
-         dev_alloc((void**)&d_sum_ptrs, sizeof(double*) * (nvals ? nvals : 1),
-                        g.stream));
+         sum_ptrs_buf.alloc(sizeof(double*) * (nvals ? nvals : 1)));
   HF_HIP("hf_groupby_compact",
-         dev_alloc((void**)&d_cnt_ptrs, sizeof(int64_t*) * (nvals ? nvals : 1),
-                        g.stream));
+         cnt_ptrs_buf.alloc(sizeof(int64_t*) * (nvals ? nvals : 1)));
+  double** d_sum_ptrs = sum_ptrs_buf.as<double*>();
+  int64_t** d_cnt_ptrs = cnt_ptrs_buf.as<int64_t*>();
   HF_HIP("hf_groupby_compact",
          hipMemcpyAsync(d_sum_ptrs, h_sum_ptrs.data(), sizeof(double*) * nvals,
                         hipMemcpyHostToDevice, g.stream));
-  if (counts && out_counts)
+  if (want_counts)
     HF_HIP("hf_groupby_compact",
            hipMemcpyAsync(d_cnt_ptrs, h_cnt_ptrs.data(), sizeof(int64_t*) * nvals,
                           hipMemcpyHostToDevice, g.stream));
-  const bool want_counts = counts && out_counts;
-  rc = timed_launch("gb_compact_scatter", [&] {
-    if (want_counts)
-      hipLaunchKernelGGL(k_compact_scatter<true>, dim3((uint32_t)ntiles), dim3(BLOCK),
-                         0, g.stream, (const double*)sums,
-                         (const unsigned long long*)rowcnt,
-                         (const unsigned long long*)counts, nvals, key_min, n_slots,
-                         d_tiles, (int64_t*)(*out_keys)->dptr, d_sum_ptrs, d_cnt_ptrs);
-    else
-      hipLaunchKernelGGL(k_compact_scatter<false>, dim3((uint32_t)ntiles), dim3(BLOCK),
-                         0, g.stream, (const double*)sums,
-                         (const unsigned long long*)rowcnt,
-                         (const unsigned long long*)counts, nvals, key_min, n_slots,
-                         d_tiles, (int64_t*)(*out_keys)->dptr, d_sum_ptrs, d_cnt_ptrs);
+  rc = with_bool(want_counts, [&](auto cTag) {
+    return timed_launch("gb_compact_scatter", [&] {
+      hipLaunchKernelGGL(k_compact_scatter<decltype(cTag)::value>,
+                         dim3((uint32_t)ntiles), dim3(BLOCK), 0, g.stream,
+                         (const double*)sums, (const unsigned long long*)rowcnt,
+                         (const unsigned long long*)counts, nvals, key_min,
+                         n_slots, d_tiles, o.keys.data<int64_t>(), d_sum_ptrs,
+                         d_cnt_ptrs);
+    });
   });
-  dev_free(d_tiles, g.stream);
-  dev_free(d_sum_ptrs, g.stream);
-  dev_free(d_cnt_ptrs, g.stream);
   if (rc != HF_OK) return rc;
+  o.commit(out_keys, out_sums, out_counts);
   *n_groups = total;
   return HF_OK;
 }
@@ -3896,9 +3952,10 @@ int hf_col_concat(const hf_col* const* cols, int ncols, hf_col** out) {
       return set_err(HF_ERR_ARG, "hf_col_concat", "dtype mismatch");
     total += cols[i]->len;
   }
-  int rc = hf_col_alloc(total, dt, out);
+  ColOut o;
+  int rc = o.alloc(total, dt);
   if (rc != HF_OK) return rc;
-  char* dst = (char*)(*out)->dptr;
+  char* dst = o.data<char>();
   const int64_t esz = dtype_size(dt);
   for (int i = 0; i < ncols; ++i) {
     const int64_t bytes = cols[i]->len * esz;
@@ -3908,6 +3965,7 @@ int hf_col_concat(const hf_col* const* cols, int ncols, hf_col** out) {
                             hipMemcpyDeviceToDevice, g.stream));
     dst += bytes;
   }
+  o.commit(out);
   return HF_OK;
 }
 
@@ -3977,8 +4035,7 @@ int hf_groupby_hash_accum(const hf_col* keys, const hf_col* const* vals,
   }
   const int64_t n = keys->len;
   if (n == 0) return HF_OK;
-  unsigned long long* d_full =
-      (unsigned long long*)((char*)g.d_scratch + SCRATCH_HASH_FULL);
+  unsigned long long* d_full = scratch_at(SCRATCH_HASH_FULL);
   return with_nvals<GB_MAX_VALS>(nvals, [&](auto nvTag) {
     return with_bool(counts != 0, [&](auto cTag) {
       return with_aop(agg_op, [&](auto aTag) {
@@ -4007,8 +4064,7 @@ int hf_groupby_hash_compact(uintptr_t tkey, uintptr_t sums, uintptr_t rowcnt,
     return set_err(HF_ERR_ARG, "hf_groupby_hash_compact", "bad args");
   // surface "table full" from the accumulate phase
   unsigned long long h_full = 0;
-  unsigned long long* d_full =
-      (unsigned long long*)((char*)g.d_scratch + SCRATCH_HASH_FULL);
+  unsigned long long* d_full = scratch_at(SCRATCH_HASH_FULL);
   HF_HIP("hf_groupby_hash_compact",
          hipMemcpyAsync(&h_full, d_full, 8, hipMemcpyDeviceToHost, g.stream));
   HF_HIP("hf_groupby_hash_compact", hipStreamSynchronize(g.stream));
@@ -4021,40 +4077,39 @@ int hf_groupby_hash_compact(uintptr_t tkey, uintptr_t sums, uintptr_t rowcnt,
   const int gpu = g.gpu;
   // filter present slots (rowcnt doubles as the nonzero mask)
   hf_col mask_view{(void*)rowcnt, L, HF_INT64, gpu};
-  hf_filterplan* plan = nullptr;
+  const bool want_counts = counts && out_counts;
+  ColOut ckeys;
+  std::vector<ColOut> csums(nvals), ccnts(counts ? nvals : 0);
   int64_t kept = 0;
-  int rc = hf_filter_plan(&mask_view, &plan, &kept);
-  if (rc != HF_OK) return rc;
-  hf_col tkey_view{(void*)tkey, L, HF_INT64, gpu};
-  hf_col* ckeys = nullptr;
-  rc = hf_filter_apply(plan, &tkey_view, &ckeys);
-  std::vector<hf_col*> csums((size_t)(nvals ? nvals : 1), nullptr);
-  std::vector<hf_col*> ccnts((size_t)(nvals ? nvals : 1), nullptr);
-  for (int c = 0; c < nvals && rc == HF_OK; ++c) {
-    hf_col sv{(char*)sums + (int64_t)c * L * 8, L, HF_FLOAT64, gpu};
-    rc = hf_filter_apply(plan, &sv, &csums[c]);
-    if (rc == HF_OK && counts) {
-      hf_col cv{(char*)counts + (int64_t)c * L * 8, L, HF_INT64, gpu};
-      rc = hf_filter_apply(plan, &cv, &ccnts[c]);
+  {
+    hf_filterplan* plan = nullptr;
+    int rc = hf_filter_plan(&mask_view, &plan, &kept);
+    if (rc != HF_OK) return rc;
+    const PlanOwner plan_owner(plan, hf_filter_plan_free);
+    hf_col tkey_view{(void*)tkey, L, HF_INT64, gpu};
+    rc = hf_filter_apply(plan, &tkey_view, ckeys.slot());
+    for (int c = 0; c < nvals && rc == HF_OK; ++c) {
+      hf_col sv{(char*)sums + (int64_t)c * L * 8, L, HF_FLOAT64, gpu};
+      rc = hf_filter_apply(plan, &sv, csums[c].slot());
+      if (rc == HF_OK && counts) {
+        hf_col cv{(char*)counts + (int64_t)c * L * 8, L, HF_INT64, gpu};
+        rc = hf_filter_apply(plan, &cv, ccnts[c].slot());
+      }
     }
+    if (rc != HF_OK) return rc;
   }
-  hf_filter_plan_free(plan);
   // sort surviving keys (wide radix handles any int64 range) and gather
-  hf_col* perm = nullptr;
-  if (rc == HF_OK) rc = hf_sort_perm(ckeys, 1, &perm);
-  if (rc == HF_OK) rc = hf_gather(ckeys, perm, out_keys);
+  ColOut perm;
+  GroupOut o(nvals, want_counts);
+  int rc = hf_sort_perm(ckeys.get(), 1, perm.slot());
+  if (rc == HF_OK) rc = hf_gather(ckeys.get(), perm.get(), o.keys.slot());
   for (int c = 0; c < nvals && rc == HF_OK; ++c) {
-    rc = hf_gather(csums[c], perm, &out_sums[c]);
-    if (rc == HF_OK && counts && out_counts)
-      rc = hf_gather(ccnts[c], perm, &out_counts[c]);
-  }
-  hf_col_free(ckeys);
-  hf_col_free(perm);
-  for (int c = 0; c < nvals; ++c) {
-    hf_col_free(csums[c]);
-    hf_col_free(ccnts[c]);
+    rc = hf_gather(csums[c].get(), perm.get(), o.sums[c].slot());
+    if (rc == HF_OK && want_counts)
+      rc = hf_gather(ccnts[c].get(), perm.get(), o.cnts[c].slot());
   }
   if (rc != HF_OK) return rc;
+  o.commit(out_keys, out_sums, out_counts);
   *n_groups = kept;
   return HF_OK;
 }
@@ -4068,46 +4123,36 @@ int hf_cumsum(const hf_col* col, int agg_op, hf_col** out) {
       agg_op != HF_AGG_MAX && agg_op != HF_AGG_PROD)
     return set_err(HF_ERR_ARG, "hf_cumsum", "bad agg_op");
   const int64_t n = col->len;
-  int rc = hf_col_alloc(n, col->dtype, out);
+  ColOut o;
+  int rc = o.alloc(n, col->dtype);
   if (rc != HF_OK) return rc;
-  if (n == 0) return HF_OK;
+  if (n == 0) { o.commit(out); return HF_OK; }
   const int64_t ntiles = (n + FILT_TILE - 1) / FILT_TILE;
-  void* d_ts = nullptr;
-  HF_HIP("hf_cumsum", dev_alloc(&d_ts, ntiles * 8, g.stream));
-  auto run = [&](auto tTag, auto opTag) -> int {
-    using T = decltype(tTag);
-    constexpr int OP = decltype(opTag)::value;
-    int r2 = timed_launch("cumsum_tiles", [&] {
-      hipLaunchKernelGGL((k_cumsum_tiles<T, OP>), dim3((uint32_t)ntiles),
-                         dim3(BLOCK), 0, g.stream, (const T*)col->dptr, n,
-                         (T*)d_ts);
+  DevBuf ts;
+  HF_HIP("hf_cumsum", ts.alloc(ntiles * 8));
+  rc = with_scan_op(agg_op, [&](auto opTag) {
+    return with_dtype(col->dtype, [&](auto tTag) -> int {
+      using T = decltype(tTag);
+      constexpr int OP = decltype(opTag)::value;
+      int r2 = timed_launch("cumsum_tiles", [&] {
+        hipLaunchKernelGGL((k_cumsum_tiles<T, OP>), dim3((uint32_t)ntiles),
+                           dim3(BLOCK), 0, g.stream, (const T*)col->dptr, n,
+                           ts.as<T>());
+      });
+      if (r2 != HF_OK) return r2;
+      r2 = timed_launch("cumsum_scan", [&] {
+        hipLaunchKernelGGL((k_cumsum_scan_tiles<T, OP>), dim3(1), dim3(1024),
+                           0, g.stream, ts.as<T>(), ntiles);
+      });
+      if (r2 != HF_OK) return r2;
+      return timed_launch("cumsum_apply", [&] {
+        hipLaunchKernelGGL((k_cumsum_apply<T, OP>), dim3((uint32_t)ntiles),
+                           dim3(BLOCK), 0, g.stream, (const T*)col->dptr, n,
+                           (const T*)ts.as<T>(), o.data<T>());
+      });
     });
-    if (r2 != HF_OK) return r2;
-    r2 = timed_launch("cumsum_scan", [&] {
-      hipLaunchKernelGGL((k_cumsum_scan_tiles<T, OP>), dim3(1), dim3(1024),
-                         0, g.stream, (T*)d_ts, ntiles);
-    });
-    if (r2 != HF_OK) return r2;
-    return timed_launch("cumsum_apply", [&] {
-      hipLaunchKernelGGL((k_cumsum_apply<T, OP>), dim3((uint32_t)ntiles),
-                         dim3(BLOCK), 0, g.stream, (const T*)col->dptr, n,
-                         (const T*)d_ts, (T*)(*out)->dptr);
-    });
-  };
-  auto runT = [&](auto opTag) -> int {
-    return (col->dtype == HF_FLOAT64) ? run(double{}, opTag)
-                                      : run(int64_t{}, opTag);
-  };
-  rc = agg_op == HF_AGG_MIN
-           ? runT(std::integral_constant<int, HF_AGG_MIN>{})
-       : agg_op == HF_AGG_MAX
-           ? runT(std::integral_constant<int, HF_AGG_MAX>{})
-       : agg_op == HF_AGG_PROD
-           ? runT(std::integral_constant<int, HF_AGG_PROD>{})
-           : runT(std::integral_constant<int, HF_AGG_SUM>{});
-  dev_free(d_ts, g.stream);
-  if (rc != HF_OK) { hf_col_free(*out); *out = nullptr; }
-  return rc;
+  });
+  return o.commit_if(rc, out);
 }
 
 int hf_seg_cumsum(const hf_col* col, const hf_col* heads, int agg_op,
@@ -4122,55 +4167,40 @@ int hf_seg_cumsum(const hf_col* col, const hf_col* heads, int agg_op,
       agg_op != HF_AGG_MAX && agg_op != HF_AGG_PROD)
     return set_err(HF_ERR_ARG, "hf_seg_cumsum", "bad agg_op");
   const int64_t n = col->len;
-  int rc = hf_col_alloc(n, col->dtype, out);
+  ColOut o;
+  int rc = o.alloc(n, col->dtype);
   if (rc != HF_OK) return rc;
-  if (n == 0) return HF_OK;
+  if (n == 0) { o.commit(out); return HF_OK; }
   const int64_t ntiles = (n + FILT_TILE - 1) / FILT_TILE;
-  void* d_tv = nullptr;
-  void* d_tf = nullptr;
-  rc = [&]() -> int {
-    // both tile allocs inside the lambda so the hf_col_free(*out) error
-    // path below covers an alloc failure (no *out leak)
-    HF_HIP("hf_seg_cumsum", dev_alloc(&d_tv, ntiles * 8, g.stream));
-    HF_HIP("hf_seg_cumsum", dev_alloc(&d_tf, ntiles * 4, g.stream));
-    auto run = [&](auto tTag, auto opTag) -> int {
+  DevBuf tv, tf;
+  HF_HIP("hf_seg_cumsum", tv.alloc(ntiles * 8));
+  HF_HIP("hf_seg_cumsum", tf.alloc(ntiles * 4));
+  rc = with_scan_op(agg_op, [&](auto opTag) {
+    return with_dtype(col->dtype, [&](auto tTag) -> int {
       using T = decltype(tTag);
       constexpr int OP = decltype(opTag)::value;
       int r2 = timed_launch("seg_tiles", [&] {
         hipLaunchKernelGGL((k_seg_tiles<T, OP>), dim3((uint32_t)ntiles),
                            dim3(BLOCK), 0, g.stream, (const T*)col->dptr,
-                           (const int64_t*)heads->dptr, n, (T*)d_tv,
-                           (unsigned*)d_tf);
+                           (const int64_t*)heads->dptr, n, tv.as<T>(),
+                           tf.as<unsigned>());
       });
       if (r2 != HF_OK) return r2;
       r2 = timed_launch("seg_scan", [&] {
         hipLaunchKernelGGL((k_seg_scan_tiles<T, OP>), dim3(1), dim3(1024),
-                           0, g.stream, (T*)d_tv, (unsigned*)d_tf, ntiles);
+                           0, g.stream, tv.as<T>(), tf.as<unsigned>(), ntiles);
       });
       if (r2 != HF_OK) return r2;
       return timed_launch("seg_apply", [&] {
         hipLaunchKernelGGL((k_seg_apply<T, OP>), dim3((uint32_t)ntiles),
                            dim3(BLOCK), 0, g.stream, (const T*)col->dptr,
-                           (const int64_t*)heads->dptr, n, (const T*)d_tv,
-                           (const unsigned*)d_tf, (T*)(*out)->dptr);
+                           (const int64_t*)heads->dptr, n,
+                           (const T*)tv.as<T>(),
+                           (const unsigned*)tf.as<unsigned>(), o.data<T>());
       });
-    };
-    auto runT = [&](auto opTag) -> int {
-      return (col->dtype == HF_FLOAT64) ? run(double{}, opTag)
-                                        : run(int64_t{}, opTag);
-    };
-    return agg_op == HF_AGG_MIN
-               ? runT(std::integral_constant<int, HF_AGG_MIN>{})
-           : agg_op == HF_AGG_MAX
-               ? runT(std::integral_constant<int, HF_AGG_MAX>{})
-           : agg_op == HF_AGG_PROD
-               ? runT(std::integral_constant<int, HF_AGG_PROD>{})
-               : runT(std::integral_constant<int, HF_AGG_SUM>{});
-  }();
-  if (d_tf) dev_free(d_tf, g.stream);
-  if (d_tv) dev_free(d_tv, g.stream);
-  if (rc != HF_OK) { hf_col_free(*out); *out = nullptr; }
-  return rc;
+    });
+  });
+  return o.commit_if(rc, out);
 }
 
 int hf_ewm_mean(const hf_col* col, const hf_col* heads, double alpha,
@@ -4188,9 +4218,10 @@ int hf_ewm_mean(const hf_col* col, const hf_col* heads, double alpha,
     return set_err(HF_ERR_ARG, "hf_ewm_mean",
                    "heads must be an int64 0/1 column of the same length");
   const int64_t n = col->len;
-  int rc = hf_col_alloc(n, HF_FLOAT64, out);
+  ColOut o;
+  int rc = o.alloc(n, HF_FLOAT64);
   if (rc != HF_OK) return rc;
-  if (n == 0) return HF_OK;
+  if (n == 0) { o.commit(out); return HF_OK; }
   const int64_t ntiles = (n + FILT_TILE - 1) / FILT_TILE;
   EwPar k;
   k.d = 1.0 - alpha;
@@ -4198,14 +4229,13 @@ int hf_ewm_mean(const hf_col* col, const hf_col* heads, double alpha,
   k.pval = adjust ? k.d : 0.0;
   k.pnan = ignore_na ? 1.0 : k.d;
   k.thresh = min_periods > 1 ? min_periods : 1;
-  void* d_tw = nullptr;
-  void* d_tm = nullptr;
-  rc = [&]() -> int {
-    HF_HIP("hf_ewm_mean",
-           dev_alloc(&d_tw, ntiles * (int64_t)sizeof(EwW), g.stream));
-    HF_HIP("hf_ewm_mean",
-           dev_alloc(&d_tm, ntiles * (int64_t)sizeof(EwM), g.stream));
-    auto run = [&](auto tTag, auto hTag) -> int {
+  DevBuf tw, tm;
+  HF_HIP("hf_ewm_mean", tw.alloc(ntiles * (int64_t)sizeof(EwW)));
+  HF_HIP("hf_ewm_mean", tm.alloc(ntiles * (int64_t)sizeof(EwM)));
+  EwW* d_tw = tw.as<EwW>();
+  EwM* d_tm = tm.as<EwM>();
+  rc = with_bool(heads != nullptr, [&](auto hTag) {
+    return with_dtype(col->dtype, [&](auto tTag) -> int {
       using T = decltype(tTag);
       constexpr bool H = decltype(hTag)::value;
       const T* in = (const T*)col->dptr;
@@ -4213,40 +4243,32 @@ int hf_ewm_mean(const hf_col* col, const hf_col* heads, double alpha,
       const dim3 grid((uint32_t)ntiles);
       int r2 = timed_launch("ewm_w_tiles", [&] {
         hipLaunchKernelGGL((k_ewm_w_tiles<T, H>), grid, dim3(BLOCK), 0,
-                           g.stream, in, hd, n, k, (EwW*)d_tw);
+                           g.stream, in, hd, n, k, d_tw);
       });
       if (r2 != HF_OK) return r2;
       r2 = timed_launch("ewm_w_scan", [&] {
         hipLaunchKernelGGL((k_ewm_scan_tiles<EwW>), dim3(1), dim3(1024), 0,
-                           g.stream, (EwW*)d_tw, ntiles);
+                           g.stream, d_tw, ntiles);
       });
       if (r2 != HF_OK) return r2;
       r2 = timed_launch("ewm_m_tiles", [&] {
         hipLaunchKernelGGL((k_ewm_m_tiles<T, H>), grid, dim3(BLOCK), 0,
-                           g.stream, in, hd, n, k, (const EwW*)d_tw,
-                           (EwM*)d_tm);
+                           g.stream, in, hd, n, k, (const EwW*)d_tw, d_tm);
       });
       if (r2 != HF_OK) return r2;
       r2 = timed_launch("ewm_m_scan", [&] {
         hipLaunchKernelGGL((k_ewm_scan_tiles<EwM>), dim3(1), dim3(1024), 0,
-                           g.stream, (EwM*)d_tm, ntiles);
+                           g.stream, d_tm, ntiles);
       });
       if (r2 != HF_OK) return r2;
       return timed_launch("ewm_apply", [&] {
         hipLaunchKernelGGL((k_ewm_apply<T, H>), grid, dim3(BLOCK), 0,
                            g.stream, in, hd, n, k, (const EwW*)d_tw,
-                           (const EwM*)d_tm, (double*)(*out)->dptr);
+                           (const EwM*)d_tm, o.data<double>());
       });
-    };
-    return with_bool(heads != nullptr, [&](auto hTag) -> int {
-      return (col->dtype == HF_FLOAT64) ? run(double{}, hTag)
-                                        : run(int64_t{}, hTag);
     });
-  }();
-  if (d_tm) dev_free(d_tm, g.stream);
-  if (d_tw) dev_free(d_tw, g.stream);
-  if (rc != HF_OK) { hf_col_free(*out); *out = nullptr; }
-  return rc;
+  });
+  return o.commit_if(rc, out);
 }
 
 int hf_cross_idx(int64_t nl, int64_t nr, hf_col** lidx, hf_col** ridx) {
@@ -4254,21 +4276,25 @@ int hf_cross_idx(int64_t nl, int64_t nr, hf_col** lidx, hf_col** ridx) {
   if (!lidx || !ridx || nl < 0 || nr <= 0)
     return set_err(HF_ERR_ARG, "hf_cross_idx", "bad args");
   const int64_t n = nl * nr;
-  int rc = hf_col_alloc(n, HF_INT64, lidx);
-  if (rc != HF_OK) return rc;
-  rc = hf_col_alloc(n, HF_INT64, ridx);
-  if (rc != HF_OK) { hf_col_free(*lidx); *lidx = nullptr; return rc; }
-  if (n == 0) return HF_OK;
-  rc = timed_launch("cross_idx", [&] {
-    hipLaunchKernelGGL(k_cross_idx, dim3((uint32_t)grid_for(n)), dim3(BLOCK),
-                       0, g.stream, n, nr, (int64_t*)(*lidx)->dptr,
-                       (int64_t*)(*ridx)->dptr);
-  });
-  if (rc != HF_OK) {
-    hf_col_free(*lidx); hf_col_free(*ridx);
-    *lidx = *ridx = nullptr;
+  ColOut o[2];
+  for (ColOut& c : o) {
+    const int rc = c.alloc(n, HF_INT64);
+    if (rc != HF_OK) return rc;
   }
-  return rc;
+  if (n > 0) {
+    const int rc = timed_launch("cross_idx", [&] {
+      hipLaunchKernelGGL(k_cross_idx, dim3((uint32_t)grid_for(n)), dim3(BLOCK),
+                         0, g.stream, n, nr, o[0].data<int64_t>(),
+                         o[1].data<int64_t>());
+    });
+    if (rc != HF_OK) {
+      *lidx = *ridx = nullptr;
+      return rc;
+    }
+  }
+  o[0].commit(lidx);
+  o[1].commit(ridx);
+  return HF_OK;
 }
 
 int hf_scatter(const hf_col* col, const hf_col* idx, hf_col** out) {
@@ -4277,23 +4303,20 @@ int hf_scatter(const hf_col* col, const hf_col* idx, hf_col** out) {
   if (idx->dtype != HF_INT64 || idx->len != col->len)
     return set_err(HF_ERR_ARG, "hf_scatter",
                    "index must be an int64 permutation of the column");
-  int rc = hf_col_alloc(col->len, col->dtype, out);
+  ColOut o;
+  int rc = o.alloc(col->len, col->dtype);
   if (rc != HF_OK) return rc;
   const int64_t n = col->len;
-  if (n == 0) return HF_OK;
-  rc = timed_launch("scatter", [&] {
-    if (col->dtype == HF_FLOAT64)
-      hipLaunchKernelGGL((k_scatter<double>), dim3((uint32_t)grid_for(n)),
-                         dim3(BLOCK), 0, g.stream, (const double*)col->dptr,
-                         (const int64_t*)idx->dptr, (double*)(*out)->dptr, n);
-    else
-      hipLaunchKernelGGL((k_scatter<int64_t>), dim3((uint32_t)grid_for(n)),
-                         dim3(BLOCK), 0, g.stream, (const int64_t*)col->dptr,
-                         (const int64_t*)idx->dptr, (int64_t*)(*out)->dptr,
-                         n);
+  if (n == 0) { o.commit(out); return HF_OK; }
+  rc = with_dtype(col->dtype, [&](auto tTag) {
+    using T = decltype(tTag);
+    return timed_launch("scatter", [&] {
+      hipLaunchKernelGGL((k_scatter<T>), dim3((uint32_t)grid_for(n)),
+                         dim3(BLOCK), 0, g.stream, (const T*)col->dptr,
+                         (const int64_t*)idx->dptr, o.data<T>(), n);
+    });
   });
-  if (rc != HF_OK) { hf_col_free(*out); *out = nullptr; }
-  return rc;
+  return o.commit_if(rc, out);
 }
 
 int hf_ordered_i64(const hf_col* col, int direction, hf_col** out) {
@@ -4305,24 +4328,21 @@ int hf_ordered_i64(const hf_col* col, int direction, hf_col** out) {
                    direction ? "inverse needs an int64 column"
                              : "forward needs a float64 column");
   const int64_t n = col->len;
-  int rc = hf_col_alloc(n, direction ? HF_FLOAT64 : HF_INT64, out);
+  ColOut o;
+  int rc = o.alloc(n, direction ? HF_FLOAT64 : HF_INT64);
   if (rc != HF_OK) return rc;
-  if (n > 0) {
+  if (n > 0)
     rc = timed_launch("f64_ordered", [&] {
       if (direction)
         hipLaunchKernelGGL(k_ordered_f64, dim3((uint32_t)grid_for(n)),
                            dim3(BLOCK), 0, g.stream,
-                           (const int64_t*)col->dptr, (double*)(*out)->dptr,
-                           n);
+                           (const int64_t*)col->dptr, o.data<double>(), n);
       else
         hipLaunchKernelGGL(k_f64_ordered, dim3((uint32_t)grid_for(n)),
                            dim3(BLOCK), 0, g.stream,
-                           (const double*)col->dptr,
-                           (int64_t*)(*out)->dptr, n);
+                           (const double*)col->dptr, o.data<int64_t>(), n);
     });
-    if (rc != HF_OK) { hf_col_free(*out); *out = nullptr; }
-  }
-  return rc;
+  return o.commit_if(rc, out);
 }
 
 int hf_search_sorted(const hf_col* keys, const hf_col* sorted_uniq,
@@ -4333,19 +4353,18 @@ int hf_search_sorted(const hf_col* keys, const hf_col* sorted_uniq,
   if (keys->dtype != HF_INT64 || sorted_uniq->dtype != HF_INT64)
     return set_err(HF_ERR_ARG, "hf_search_sorted", "int64 columns required");
   const int64_t n = keys->len;
-  int rc = hf_col_alloc(n, HF_INT64, out);
+  ColOut o;
+  int rc = o.alloc(n, HF_INT64);
   if (rc != HF_OK) return rc;
-  if (n > 0) {
+  if (n > 0)
     rc = timed_launch("search_sorted", [&] {
       hipLaunchKernelGGL(k_search_sorted, dim3((uint32_t)grid_for(n)),
                          dim3(BLOCK), 0, g.stream,
                          (const int64_t*)keys->dptr, n,
                          (const int64_t*)sorted_uniq->dptr,
-                         sorted_uniq->len, (int64_t*)(*out)->dptr);
+                         sorted_uniq->len, o.data<int64_t>());
     });
-    if (rc != HF_OK) { hf_col_free(*out); *out = nullptr; }
-  }
-  return rc;
+  return o.commit_if(rc, out);
 }
 
 int hf_shuffle_dest(const hf_col* keys, const int64_t* splitters, int nsplit,
@@ -4357,30 +4376,27 @@ int hf_shuffle_dest(const hf_col* keys, const int64_t* splitters, int nsplit,
   if (keys->dtype != HF_INT64)
     return set_err(HF_ERR_ARG, "hf_shuffle_dest", "keys must be int64");
   const int64_t n = keys->len;
-  int rc = hf_col_alloc(n, HF_INT64, dest);
+  ColOut o;
+  int rc = o.alloc(n, HF_INT64);
   if (rc != HF_OK) return rc;
-  int64_t* d_split = nullptr;
+  DevBuf split;
   if (nsplit) {
-    HF_HIP("hf_shuffle_dest", dev_alloc((void**)&d_split, nsplit * 8, g.stream));
+    HF_HIP("hf_shuffle_dest", split.alloc(nsplit * 8));
     HF_HIP("hf_shuffle_dest",
-           hipMemcpyAsync(d_split, splitters, nsplit * 8,
+           hipMemcpyAsync(split.as<void>(), splitters, nsplit * 8,
                           hipMemcpyHostToDevice, g.stream));
   }
   if (n > 0) {
     rc = timed_launch("shuffle_dest", [&] {
       hipLaunchKernelGGL(k_shuffle_dest, dim3((uint32_t)grid_for(n)),
                          dim3(BLOCK), 0, g.stream,
-                         (const int64_t*)keys->dptr, d_split, nsplit,
-                         (long long*)(*dest)->dptr, n);
+                         (const int64_t*)keys->dptr, split.as<int64_t>(),
+                         nsplit, o.data<long long>(), n);
     });
   }
-  if (d_split) {
-    // splitters are host memory borrowed only until the H2D lands
-    hipStreamSynchronize(g.stream);
-    dev_free(d_split, g.stream);
-  }
-  if (rc != HF_OK) { hf_col_free(*dest); *dest = nullptr; }
-  return rc;
+  // splitters are host memory borrowed only until the H2D lands
+  if (nsplit) hipStreamSynchronize(g.stream);
+  return o.commit_if(rc, dest);
 }
 
 int hf_memcpy_dd(uintptr_t dst, uintptr_t src, int64_t bytes) {
@@ -4411,30 +4427,28 @@ int hf_groupby_sorted(const hf_col* sorted_keys, const hf_col* const* vals,
                      "vals must be float64 columns of keys' length");
   const int64_t n = sorted_keys->len;
   // head flags -> filter plan (run count + tile bases)
-  hf_col* head = nullptr;
-  int rc = hf_col_alloc(n, HF_INT64, &head);
+  ColOut head;
+  int rc = head.alloc(n, HF_INT64);
   if (rc != HF_OK) return rc;
-  const std::unique_ptr<hf_col, int (*)(hf_col*)> head_owner(head,
-                                                             hf_col_free);
   if (n > 0) {
     rc = timed_launch("gb_sorted_heads", [&] {
       hipLaunchKernelGGL(k_head_flags, dim3((uint32_t)grid_for(n)),
                          dim3(BLOCK), 0, g.stream,
                          (const int64_t*)sorted_keys->dptr, n,
-                         (long long*)head->dptr);
+                         head.data<long long>());
     });
     if (rc != HF_OK) return rc;
   }
   hf_filterplan* plan = nullptr;
   int64_t C = 0;
-  rc = hf_filter_plan(head, &plan, &C);
+  rc = hf_filter_plan(head.get(), &plan, &C);
   if (rc != HF_OK) return rc;
-  const std::unique_ptr<hf_filterplan, int (*)(hf_filterplan*)> plan_owner(
-      plan, hf_filter_plan_free);
+  const PlanOwner plan_owner(plan, hf_filter_plan_free);
   // outputs: unique keys (filter of sorted keys) + per-run aggregates
-  rc = hf_filter_apply(plan, sorted_keys, out_keys);
-  if (rc != HF_OK) return rc;
   const bool cnt = want_counts != 0;
+  GroupOut o(nvals, cnt && out_counts);
+  rc = hf_filter_apply(plan, sorted_keys, o.keys.slot());
+  if (rc != HF_OK) return rc;
   // per-run aggregate buffers
   const int64_t Ca = C > 0 ? C : 1;
   DevBuf gsums_buf, growcnt_buf, gcounts_buf;
@@ -4471,7 +4485,7 @@ int hf_groupby_sorted(const hf_col* sorted_keys, const hf_col* const* vals,
               (k_segagg<decltype(aTag)::value, decltype(cTag)::value,
                         decltype(rTag)::value, decltype(vTag)::value>),
               dim3((uint32_t)ntiles), dim3(BLOCK), 0, g.stream,
-              (const long long*)head->dptr, v, n, plan_tiles(plan), gs,
+              head.data<const long long>(), v, n, plan_tiles(plan), gs,
               growcnt, gc);
         });
       };
@@ -4495,19 +4509,20 @@ int hf_groupby_sorted(const hf_col* sorted_keys, const hf_col* const* vals,
   }
   // copy the aggregates out as columns
   for (int c = 0; c < nvals; ++c) {
-    rc = hf_col_alloc(C, HF_FLOAT64, &out_sums[c]);
+    rc = o.sums[c].alloc(C, HF_FLOAT64);
     if (rc != HF_OK) return rc;
     HF_HIP("hf_groupby_sorted",
-           hipMemcpyAsync(out_sums[c]->dptr, gsums + (int64_t)c * Ca, Ca * 8,
-                          hipMemcpyDeviceToDevice, g.stream));
+           hipMemcpyAsync(o.sums[c].get()->dptr, gsums + (int64_t)c * Ca,
+                          Ca * 8, hipMemcpyDeviceToDevice, g.stream));
     if (cnt && out_counts) {
-      rc = hf_col_alloc(C, HF_INT64, &out_counts[c]);
+      rc = o.cnts[c].alloc(C, HF_INT64);
       if (rc != HF_OK) return rc;
       HF_HIP("hf_groupby_sorted",
-             hipMemcpyAsync(out_counts[c]->dptr, gcounts + (int64_t)c * Ca,
+             hipMemcpyAsync(o.cnts[c].get()->dptr, gcounts + (int64_t)c * Ca,
                             Ca * 8, hipMemcpyDeviceToDevice, g.stream));
     }
   }
+  o.commit(out_keys, out_sums, out_counts);
   *n_groups = C;
   return HF_OK;
 }
@@ -4516,17 +4531,161 @@ int hf_col_slice(const hf_col* col, int64_t start, int64_t len, hf_col** out) {
   HF_NEED_INIT("hf_col_slice");
   if (!col || !out || start < 0 || len < 0 || start + len > col->len)
     return set_err(HF_ERR_ARG, "hf_col_slice", "bad range");
-  int rc = hf_col_alloc(len, col->dtype, out);
+  ColOut o;
+  int rc = o.alloc(len, col->dtype);
   if (rc != HF_OK) return rc;
   const int64_t esz = dtype_size(col->dtype);
   if (len > 0)
     HF_HIP("hf_col_slice",
-           hipMemcpyAsync((*out)->dptr, (const char*)col->dptr + start * esz,
+           hipMemcpyAsync(o.get()->dptr, (const char*)col->dptr + start * esz,
                           len * esz, hipMemcpyDeviceToDevice, g.stream));
+  o.commit(out);
   return HF_OK;
 }
 
 // ---- join ----
+
+// HF_JOIN_DEBUG: host-side CSR verification (monotone, steps match the
+// histogram, total == rows), reported on stderr
+static void join_debug_check(const unsigned* d_cnt,
+                             const unsigned long long* d_csr, int64_t n_slots,
+                             int64_t n) {
+  std::vector<unsigned> h_cnt((size_t)n_slots);
+  std::vector<unsigned long long> h_csr((size_t)n_slots + 1);
+  hipMemcpyAsync(h_cnt.data(), d_cnt, n_slots * 4, hipMemcpyDeviceToHost,
+                 g.stream);
+  hipMemcpyAsync(h_csr.data(), d_csr, (n_slots + 1) * 8,
+                 hipMemcpyDeviceToHost, g.stream);
+  hipStreamSynchronize(g.stream);
+  unsigned long long run = 0;
+  int bad = 0;
+  for (int64_t s = 0; s < n_slots && bad < 5; ++s) {
+    if (h_csr[s] != run) {
+      fprintf(stderr,
+              "[join_debug] csr[%lld]=%llu expect %llu (cnt[s]=%u, "
+              "tile=%lld)\n",
+              (long long)s, h_csr[s], run, h_cnt[s], (long long)(s / 4096));
+      ++bad;
+    }
+    run += h_cnt[s];
+  }
+  if (h_csr[n_slots] != run)
+    fprintf(stderr, "[join_debug] csr[n]=%llu expect %llu\n", h_csr[n_slots],
+            run);
+  unsigned long long mx = 0;
+  for (int64_t s = 0; s < n_slots; ++s)
+    if (h_cnt[s] > mx) mx = h_cnt[s];
+  fprintf(stderr, "[join_debug] hist total=%llu rows=%lld max_mult=%llu "
+          "bad=%d\n", run, (long long)n, mx, bad);
+}
+
+// Per-slot histogram of the right keys (left in d_cnt) -> j->d_csr, the
+// exclusive offsets of each key's run.
+static int join_csr(const hf_col* rkeys, hf_join* j, unsigned* d_cnt,
+                    int64_t* d_tiles, int64_t ntiles) {
+  const int64_t n = j->n_right, n_slots = j->n_slots;
+  unsigned long long* d_hist_err = scratch_at(SCRATCH_JOIN_HIST_ERR);
+  int64_t* d_total = scratch_at<int64_t>(SCRATCH_NGROUPS);
+  HF_HIP("hf_join_build", DevBuf::alloc_into(j->d_csr, (n_slots + 1) * 8));
+  unsigned long long* d_csr = j->d_csr;
+  int rc = timed_launch("join_hist", [&] {
+    hipLaunchKernelGGL(k_hist_u32, dim3((uint32_t)grid_for(n)), dim3(BLOCK), 0,
+                       g.stream, (const int64_t*)rkeys->dptr, n, j->key_min,
+                       n_slots, d_cnt, d_hist_err);
+  });
+  if (rc != HF_OK) return rc;
+  rc = timed_launch("join_scan", [&] {
+    hipLaunchKernelGGL(k_tile_sums_u32, dim3((uint32_t)ntiles), dim3(BLOCK), 0,
+                       g.stream, d_cnt, n_slots, d_tiles);
+    hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, g.stream,
+                       d_tiles, ntiles, d_total);
+    hipLaunchKernelGGL(k_scan_apply_u32, dim3((uint32_t)ntiles), dim3(BLOCK),
+                       0, g.stream, d_cnt, n_slots, d_tiles, d_total, d_csr);
+  });
+  if (rc != HF_OK) return rc;
+  if (getenv("HF_JOIN_DEBUG")) join_debug_check(d_cnt, d_csr, n_slots, n);
+  return HF_OK;
+}
+
+// Allocate j's row-index and payload arrays and fill them in CSR order;
+// d_cnt is reused as the per-slot fill cursor.
+static int join_fill(const hf_col* rkeys, const JoinConstPtrs& rv, hf_join* j,
+                     unsigned* d_cnt) {
+  const int64_t n = j->n_right, n_slots = j->n_slots;
+  unsigned long long* d_fix_err = scratch_at(SCRATCH_JOIN_FIXUP_ERR);
+  HF_HIP("hf_join_build", hipMemsetAsync(d_cnt, 0, n_slots * 4, g.stream));
+  const int64_t alloc_n = n > 0 ? n : 1;
+  HF_HIP("hf_join_build", DevBuf::alloc_into(j->d_jidx, alloc_n * 4));
+  JoinPtrs jv{};
+  for (int c = 0; c < j->nr; ++c) {
+    HF_HIP("hf_join_build", DevBuf::alloc_into(j->d_jval[c], alloc_n * 8));
+    jv.vals[c] = j->d_jval[c];
+  }
+  return with_nvals<GB_MAX_VALS>(j->nr, [&](auto nrTag) {
+    constexpr int NR = decltype(nrTag)::value;
+    int r2 = timed_launch("join_fill", [&] {
+      hipLaunchKernelGGL((k_join_fill<NR>), dim3((uint32_t)grid_for(n)),
+                         dim3(BLOCK), 0, g.stream, (const int64_t*)rkeys->dptr,
+                         rv, n, j->key_min, n_slots, j->d_csr, d_cnt,
+                         j->d_jidx, jv);
+    });
+    if (r2 != HF_OK) return r2;
+    return timed_launch("join_fixup", [&] {
+      hipLaunchKernelGGL((k_join_fixup<NR>), dim3(2048), dim3(BLOCK), 0,
+                         g.stream, j->d_csr, n_slots, j->d_jidx, jv, d_fix_err);
+    });
+  });
+}
+
+// Surface the hist/fixup error words; a key beyond the in-thread fixup's
+// duplicate cap refills j from a stable sort.
+static int join_check(const hf_col* rkeys, const hf_col* const* rvals,
+                      hf_join* j) {
+  const int64_t n = j->n_right;
+  unsigned long long* d_hist_err = scratch_at(SCRATCH_JOIN_HIST_ERR);
+  unsigned long long* d_fix_err = scratch_at(SCRATCH_JOIN_FIXUP_ERR);
+  unsigned long long h_err[2] = {0, 0};
+  HF_HIP("hf_join_build",
+         hipMemcpyAsync(&h_err[0], d_hist_err, 8, hipMemcpyDeviceToHost,
+                        g.stream));
+  HF_HIP("hf_join_build",
+         hipMemcpyAsync(&h_err[1], d_fix_err, 8, hipMemcpyDeviceToHost,
+                        g.stream));
+  HF_HIP("hf_join_build", hipStreamSynchronize(g.stream));
+  if (h_err[0]) {
+    hipMemsetAsync(d_hist_err, 0, 8, g.stream);
+    hipMemsetAsync(d_fix_err, 0, 8, g.stream);
+    char buf[160];
+    snprintf(buf, sizeof buf,
+             "%llu right keys outside [key_min, key_min+n_slots)",
+             h_err[0]);
+    return set_err(HF_ERR_ARG, "hf_join_build", buf);
+  }
+  if (!h_err[1]) return HF_OK;
+  // keys beyond the 4096-duplicate in-thread fixup (round 2): rebuild
+  // ORDER-CORRECT from a stable ascending key sort — within equal keys
+  // the stable sort preserves original right order, which is exactly
+  // the CSR layout (the offsets are fill-independent and already
+  // computed).  Removes the per-key multiplicity cap entirely.
+  hipMemsetAsync(d_fix_err, 0, 8, g.stream);
+  ColOut perm;
+  int rc = hf_sort_perm(rkeys, 1, perm.slot());
+  if (rc != HF_OK) return rc;
+  rc = timed_launch("join_sortfill", [&] {
+    hipLaunchKernelGGL(k_i64_to_u32, dim3((uint32_t)grid_for(n)),
+                       dim3(BLOCK), 0, g.stream, perm.data<const int64_t>(),
+                       j->d_jidx, n);
+  });
+  for (int c = 0; c < j->nr && rc == HF_OK; ++c) {
+    ColOut sv;
+    rc = hf_gather(rvals[c], perm.get(), sv.slot());
+    if (rc != HF_OK) break;
+    if (hipMemcpyAsync(j->d_jval[c], sv.get()->dptr, n * 8,
+                       hipMemcpyDeviceToDevice, g.stream) != hipSuccess)
+      rc = set_err(HF_ERR_HIP, "hf_join_build", "sortfill copy");
+  }
+  return rc;
+}
 
 int hf_join_build(const hf_col* rkeys, const hf_col* const* rvals, int nr,
                   int64_t key_min, int64_t n_slots, hf_join** out) {
@@ -4548,156 +4707,29 @@ int hf_join_build(const hf_col* rkeys, const hf_col* const* rvals, int nr,
                      "right vals must be 8-byte columns of keys' length");
     rv.vals[c] = (const double*)rvals[c]->dptr;
   }
-  const int64_t n = rkeys->len;
-  unsigned long long* d_hist_err =
-      (unsigned long long*)((char*)g.d_scratch + SCRATCH_JOIN_HIST_ERR);
-  unsigned long long* d_fix_err =
-      (unsigned long long*)((char*)g.d_scratch + SCRATCH_JOIN_FIXUP_ERR);
-  int64_t* d_total = (int64_t*)((char*)g.d_scratch + SCRATCH_NGROUPS);
-  unsigned* d_cnt = nullptr;
-  int64_t* d_tiles = nullptr;
-  unsigned long long* d_csr = nullptr;
-  const int64_t ntiles = (n_slots + JOIN_TILE - 1) / JOIN_TILE;
-  HF_HIP("hf_join_build", dev_alloc((void**)&d_cnt, n_slots * 4, g.stream));
-  HF_HIP("hf_join_build", hipMemsetAsync(d_cnt, 0, n_slots * 4, g.stream));
-  HF_HIP("hf_join_build",
-         dev_alloc((void**)&d_tiles, ntiles * 8, g.stream));
-  HF_HIP("hf_join_build",
-         dev_alloc((void**)&d_csr, (n_slots + 1) * 8, g.stream));
-  int rc = timed_launch("join_hist", [&] {
-    hipLaunchKernelGGL(k_hist_u32, dim3((uint32_t)grid_for(n)), dim3(BLOCK), 0,
-                       g.stream, (const int64_t*)rkeys->dptr, n, key_min,
-                       n_slots, d_cnt, d_hist_err);
-  });
-  if (rc != HF_OK) return rc;
-  rc = timed_launch("join_scan", [&] {
-    hipLaunchKernelGGL(k_tile_sums_u32, dim3((uint32_t)ntiles), dim3(BLOCK), 0,
-                       g.stream, d_cnt, n_slots, d_tiles);
-    hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, g.stream,
-                       d_tiles, ntiles, d_total);
-    hipLaunchKernelGGL(k_scan_apply_u32, dim3((uint32_t)ntiles), dim3(BLOCK),
-                       0, g.stream, d_cnt, n_slots, d_tiles, d_total, d_csr);
-  });
-  if (rc != HF_OK) return rc;
-  if (getenv("HF_JOIN_DEBUG")) {
-    // host-side CSR verification (debug only): monotone, steps match the
-    // histogram, total == rows
-    std::vector<unsigned> h_cnt((size_t)n_slots);
-    std::vector<unsigned long long> h_csr((size_t)n_slots + 1);
-    hipMemcpyAsync(h_cnt.data(), d_cnt, n_slots * 4, hipMemcpyDeviceToHost,
-                   g.stream);
-    hipMemcpyAsync(h_csr.data(), d_csr, (n_slots + 1) * 8,
-                   hipMemcpyDeviceToHost, g.stream);
-    hipStreamSynchronize(g.stream);
-    unsigned long long run = 0;
-    int bad = 0;
-    for (int64_t s = 0; s < n_slots && bad < 5; ++s) {
-      if (h_csr[s] != run) {
-        fprintf(stderr,
-                "[join_debug] csr[%lld]=%llu expect %llu (cnt[s]=%u, "
-                "tile=%lld)\n",
-                (long long)s, h_csr[s], run, h_cnt[s], (long long)(s / 4096));
-        ++bad;
-      }
-      run += h_cnt[s];
-    }
-    if (h_csr[n_slots] != run)
-      fprintf(stderr, "[join_debug] csr[n]=%llu expect %llu\n", h_csr[n_slots],
-              run);
-    unsigned long long mx = 0;
-    for (int64_t s = 0; s < n_slots; ++s)
-      if (h_cnt[s] > mx) mx = h_cnt[s];
-    fprintf(stderr, "[join_debug] hist total=%llu rows=%lld max_mult=%llu "
-            "bad=%d\n", run, (long long)n, mx, bad);
-  }
-  // reuse d_cnt as the fill cursor
-  HF_HIP("hf_join_build", hipMemsetAsync(d_cnt, 0, n_slots * 4, g.stream));
-  hf_join* j = new hf_join{};
+  JoinOwner j(new hf_join{}, hf_join_free);
   j->key_min = key_min;
   j->n_slots = n_slots;
-  j->n_right = n;
+  j->n_right = rkeys->len;
   j->nr = nr;
-  j->d_csr = d_csr;
   for (int c = 0; c < nr; ++c) j->dtypes[c] = rvals[c]->dtype;
-  const int64_t alloc_n = n > 0 ? n : 1;
-  HF_HIP("hf_join_build",
-         dev_alloc((void**)&j->d_jidx, alloc_n * 4, g.stream));
-  JoinPtrs jv{};
-  for (int c = 0; c < nr; ++c) {
+  int rc;
+  {
+    // histogram / fill cursor and scan tiles: back to the allocator before
+    // the error-word readback and a possible sorted refill
+    const int64_t ntiles = (n_slots + JOIN_TILE - 1) / JOIN_TILE;
+    DevBuf cnt, tiles;
+    HF_HIP("hf_join_build", cnt.alloc(n_slots * 4));
     HF_HIP("hf_join_build",
-           dev_alloc((void**)&j->d_jval[c], alloc_n * 8, g.stream));
-    jv.vals[c] = j->d_jval[c];
+           hipMemsetAsync(cnt.as<void>(), 0, n_slots * 4, g.stream));
+    HF_HIP("hf_join_build", tiles.alloc(ntiles * 8));
+    rc = join_csr(rkeys, j.get(), cnt.as<unsigned>(), tiles.as<int64_t>(),
+                  ntiles);
+    if (rc == HF_OK) rc = join_fill(rkeys, rv, j.get(), cnt.as<unsigned>());
   }
-  auto fill = [&](auto nrTag) {
-    constexpr int NR = decltype(nrTag)::value;
-    int r2 = timed_launch("join_fill", [&] {
-      hipLaunchKernelGGL((k_join_fill<NR>), dim3((uint32_t)grid_for(n)),
-                         dim3(BLOCK), 0, g.stream, (const int64_t*)rkeys->dptr,
-                         rv, n, key_min, n_slots, d_csr, d_cnt, j->d_jidx, jv);
-    });
-    if (r2 != HF_OK) return r2;
-    return timed_launch("join_fixup", [&] {
-      hipLaunchKernelGGL((k_join_fixup<NR>), dim3(2048), dim3(BLOCK), 0,
-                         g.stream, d_csr, n_slots, j->d_jidx, jv, d_fix_err);
-    });
-  };
-  switch (nr) {
-#define HF_JB_CASE(NR) case NR: rc = fill(std::integral_constant<int, NR>{}); break;
-    HF_JB_CASE(0) HF_JB_CASE(1) HF_JB_CASE(2) HF_JB_CASE(3) HF_JB_CASE(4)
-    HF_JB_CASE(5) HF_JB_CASE(6) HF_JB_CASE(7) HF_JB_CASE(8)
-#undef HF_JB_CASE
-  }
-  dev_free(d_cnt, g.stream);
-  dev_free(d_tiles, g.stream);
-  if (rc != HF_OK) { hf_join_free(j); return rc; }
-  // surface hist/fixup errors
-  unsigned long long h_err[2] = {0, 0};
-  HF_HIP("hf_join_build",
-         hipMemcpyAsync(&h_err[0], d_hist_err, 8, hipMemcpyDeviceToHost,
-                        g.stream));
-  HF_HIP("hf_join_build",
-         hipMemcpyAsync(&h_err[1], d_fix_err, 8, hipMemcpyDeviceToHost,
-                        g.stream));
-  HF_HIP("hf_join_build", hipStreamSynchronize(g.stream));
-  if (h_err[0]) {
-    hipMemsetAsync(d_hist_err, 0, 8, g.stream);
-    hipMemsetAsync(d_fix_err, 0, 8, g.stream);
-    hf_join_free(j);
-    char buf[160];
-    snprintf(buf, sizeof buf,
-             "%llu right keys outside [key_min, key_min+n_slots)",
-             h_err[0]);
-    return set_err(HF_ERR_ARG, "hf_join_build", buf);
-  }
-  if (h_err[1]) {
-    // keys beyond the 4096-duplicate in-thread fixup (round 2): rebuild
-    // ORDER-CORRECT from a stable ascending key sort — within equal keys
-    // the stable sort preserves original right order, which is exactly
-    // the CSR layout (the offsets are fill-independent and already
-    // computed).  Removes the per-key multiplicity cap entirely.
-    hipMemsetAsync(d_fix_err, 0, 8, g.stream);
-    hf_col* perm = nullptr;
-    int r3 = hf_sort_perm(rkeys, 1, &perm);
-    if (r3 != HF_OK) { hf_join_free(j); return r3; }
-    r3 = timed_launch("join_sortfill", [&] {
-      hipLaunchKernelGGL(k_i64_to_u32, dim3((uint32_t)grid_for(n)),
-                         dim3(BLOCK), 0, g.stream,
-                         (const int64_t*)perm->dptr, j->d_jidx, n);
-    });
-    for (int c = 0; c < nr && r3 == HF_OK; ++c) {
-      hf_col* sv = nullptr;
-      r3 = hf_gather(rvals[c], perm, &sv);
-      if (r3 != HF_OK) break;
-      r3 = (hipMemcpyAsync(j->d_jval[c], sv->dptr, n * 8,
-                           hipMemcpyDeviceToDevice, g.stream) == hipSuccess)
-               ? HF_OK
-               : set_err(HF_ERR_HIP, "hf_join_build", "sortfill copy");
-      hf_col_free(sv);
-    }
-    hf_col_free(perm);
-    if (r3 != HF_OK) { hf_join_free(j); return r3; }
-  }
-  *out = j;
+  if (rc == HF_OK) rc = join_check(rkeys, rvals, j.get());
+  if (rc != HF_OK) return rc;
+  *out = j.release();
   return HF_OK;
 }
 
@@ -4722,16 +4754,15 @@ int hf_join_probe(const hf_join* j, const hf_col* lkeys, hf_col** out_keys,
     return set_err(HF_ERR_ARG, "hf_join_probe", "left keys must be int64");
   const int64_t n = lkeys->len;
   const int64_t ntiles = n > 0 ? (n + JOIN_TILE - 1) / JOIN_TILE : 1;
-  unsigned long long* d_offs = nullptr;
-  unsigned* d_cnts = nullptr;
-  int64_t* d_tiles = nullptr;
-  int64_t* d_total = (int64_t*)((char*)g.d_scratch + SCRATCH_NGROUPS);
+  int64_t* d_total = scratch_at<int64_t>(SCRATCH_NGROUPS);
   const int64_t alloc_n = n > 0 ? n : 1;
-  HF_HIP("hf_join_probe",
-         dev_alloc((void**)&d_offs, alloc_n * 8, g.stream));
-  HF_HIP("hf_join_probe",
-         dev_alloc((void**)&d_cnts, alloc_n * 4, g.stream));
-  HF_HIP("hf_join_probe", dev_alloc((void**)&d_tiles, ntiles * 8, g.stream));
+  DevBuf offs, cnts, tiles;
+  HF_HIP("hf_join_probe", offs.alloc(alloc_n * 8));
+  HF_HIP("hf_join_probe", cnts.alloc(alloc_n * 4));
+  HF_HIP("hf_join_probe", tiles.alloc(ntiles * 8));
+  unsigned long long* d_offs = offs.as<unsigned long long>();
+  unsigned* d_cnts = cnts.as<unsigned>();
+  int64_t* d_tiles = tiles.as<int64_t>();
   HF_HIP("hf_join_probe", hipMemsetAsync(d_tiles, 0, ntiles * 8, g.stream));
   int rc = HF_OK;
   if (n > 0) {
@@ -4748,41 +4779,36 @@ int hf_join_probe(const hf_join* j, const hf_col* lkeys, hf_col** out_keys,
   HF_HIP("hf_join_probe",
          hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, g.stream));
   HF_HIP("hf_join_probe", hipStreamSynchronize(g.stream));
-  rc = hf_col_alloc(total, HF_INT64, out_keys);
+  ColOut keys, lidx;
+  std::vector<ColOut> rcols(j->nr);
+  rc = keys.alloc(total, HF_INT64);
   if (rc != HF_OK) return rc;
-  rc = hf_col_alloc(total, HF_INT64, out_lidx);
+  rc = lidx.alloc(total, HF_INT64);
   if (rc != HF_OK) return rc;
   JoinPtrs outr{};
   JoinConstPtrs jvc{};
   for (int c = 0; c < j->nr; ++c) {
-    rc = hf_col_alloc(total, j->dtypes[c], &out_rcols[c]);
+    rc = rcols[c].alloc(total, j->dtypes[c]);
     if (rc != HF_OK) return rc;
-    outr.vals[c] = (double*)out_rcols[c]->dptr;
+    outr.vals[c] = rcols[c].data<double>();
     jvc.vals[c] = j->d_jval[c];
   }
   if (n > 0 && total > 0) {
-    auto emit = [&](auto nrTag) {
+    rc = with_nvals<GB_MAX_VALS>(j->nr, [&](auto nrTag) {
       constexpr int NR = decltype(nrTag)::value;
       return timed_launch("join_probe_emit", [&] {
         hipLaunchKernelGGL((k_probe_emit<NR>), dim3((uint32_t)ntiles),
                            dim3(BLOCK), 0, g.stream,
                            (const int64_t*)lkeys->dptr, n, (int64_t)0, d_offs,
                            d_cnts, d_tiles, j->d_jidx, jvc,
-                           (int64_t*)(*out_keys)->dptr,
-                           (int64_t*)(*out_lidx)->dptr, outr);
+                           keys.data<int64_t>(), lidx.data<int64_t>(), outr);
       });
-    };
-    switch (j->nr) {
-#define HF_JP_CASE(NR) case NR: rc = emit(std::integral_constant<int, NR>{}); break;
-      HF_JP_CASE(0) HF_JP_CASE(1) HF_JP_CASE(2) HF_JP_CASE(3) HF_JP_CASE(4)
-      HF_JP_CASE(5) HF_JP_CASE(6) HF_JP_CASE(7) HF_JP_CASE(8)
-#undef HF_JP_CASE
-    }
+    });
+    if (rc != HF_OK) return rc;
   }
-  dev_free(d_offs, g.stream);
-  dev_free(d_cnts, g.stream);
-  dev_free(d_tiles, g.stream);
-  if (rc != HF_OK) return rc;
+  keys.commit(out_keys);
+  lidx.commit(out_lidx);
+  for (int c = 0; c < j->nr; ++c) rcols[c].commit(&out_rcols[c]);
   *n_out = total;
   return HF_OK;
 }
@@ -4792,22 +4818,42 @@ int hf_gather(const hf_col* col, const hf_col* idx, hf_col** out) {
   if (!col || !idx || !out) return set_err(HF_ERR_ARG, "hf_gather", "null");
   if (idx->dtype != HF_INT64)
     return set_err(HF_ERR_ARG, "hf_gather", "index must be int64");
-  int rc = hf_col_alloc(idx->len, col->dtype, out);
+  ColOut o;
+  int rc = o.alloc(idx->len, col->dtype);
   if (rc != HF_OK) return rc;
   const int64_t n = idx->len;
-  if (n == 0) return HF_OK;
+  if (n == 0) { o.commit(out); return HF_OK; }
   rc = timed_launch("gather", [&] {
     if (col->dtype == HF_FLOAT64)
       hipLaunchKernelGGL(k_gather_f64, dim3((uint32_t)grid_for(n)), dim3(BLOCK),
                          0, g.stream, (const double*)col->dptr,
-                         (const int64_t*)idx->dptr, (double*)(*out)->dptr, n);
+                         (const int64_t*)idx->dptr, o.data<double>(), n);
     else
       hipLaunchKernelGGL(k_gather_i64, dim3((uint32_t)grid_for(n)), dim3(BLOCK),
                          0, g.stream, (const int64_t*)col->dptr,
-                         (const int64_t*)idx->dptr, (int64_t*)(*out)->dptr, n);
+                         (const int64_t*)idx->dptr, o.data<int64_t>(), n);
   });
-  if (rc != HF_OK) { hf_col_free(*out); *out = nullptr; }
-  return rc;
+  return o.commit_if(rc, out);
+}
+
+// The digit-offset part of one radix pass, shared by the narrow and the wide
+// sort: per-tile digit counts C[tile][digit] -> exclusive scatter offsets
+// offs[digit][tile].  Called inside the pass's timed_launch.
+static void sort_digit_offsets(const unsigned* C, unsigned* CT,
+                               int64_t* scan_tiles, unsigned long long* offs,
+                               int64_t ntiles) {
+  const int64_t L = ntiles * 256;
+  const int64_t scan_tiles_n = (L + JOIN_TILE - 1) / JOIN_TILE;
+  int64_t* d_total = scratch_at<int64_t>(SCRATCH_NGROUPS);
+  hipLaunchKernelGGL(k_transpose256, dim3((uint32_t)((ntiles + 31) / 32), 8),
+                     dim3(1024), 0, g.stream, C, CT, ntiles);
+  hipLaunchKernelGGL(k_tile_sums_u32, dim3((uint32_t)scan_tiles_n),
+                     dim3(BLOCK), 0, g.stream, CT, L, scan_tiles);
+  hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, g.stream,
+                     scan_tiles, scan_tiles_n, d_total);
+  hipLaunchKernelGGL(k_scan_apply_u32, dim3((uint32_t)scan_tiles_n),
+                     dim3(BLOCK), 0, g.stream, CT, L, scan_tiles, d_total,
+                     offs);
 }
 
 int hf_sort_perm(const hf_col* keys, int ascending, hf_col** out_perm) {
@@ -4816,62 +4862,58 @@ int hf_sort_perm(const hf_col* keys, int ascending, hf_col** out_perm) {
   if (keys->dtype != HF_INT64)
     return set_err(HF_ERR_ARG, "hf_sort_perm", "sort key must be int64");
   const int64_t n = keys->len;
-  int rc = hf_col_alloc(n, HF_INT64, out_perm);
-  if (rc != HF_OK) return rc;
-  if (n == 0) return HF_OK;
   if (n >= (1LL << 31))
     return set_err(HF_ERR_UNSUPPORTED, "hf_sort_perm",
                    "partition too large (u32 origin indices)");
-  hf_reduce_result r;
-  rc = hf_reduce(keys, &r);
+  hf_reduce_result r{};
+  int rc = n > 0 ? hf_reduce(keys, &r) : HF_OK;
   if (rc != HF_OK) return rc;
+  ColOut perm;
+  rc = perm.alloc(n, HF_INT64);
+  if (rc != HF_OK) return rc;
+  if (n == 0) { perm.commit(out_perm); return HF_OK; }
   const int64_t key_min = r.imn;
   const uint64_t span = (uint64_t)r.imx - (uint64_t)r.imn;  // mod-2^64 safe
-  if (span >= (1ULL << 27)) {
-    // wide path: u64 shifted keys + u32 origins, up to 8 digit passes
-    int bits = 0;
-    while (bits < 64 && (span >> bits) != 0) ++bits;
-    const int passes = (bits + 7) / 8;
-    const int64_t ntiles = (n + SORT_TILE - 1) / SORT_TILE;
-    const int64_t L = ntiles * 256;
-    unsigned long long *kA = nullptr, *kB = nullptr, *offs = nullptr;
-    unsigned *iA = nullptr, *iB = nullptr, *C = nullptr, *CT = nullptr;
-    int64_t* scan_tiles = nullptr;
-    const int64_t scan_tiles_n = (L + JOIN_TILE - 1) / JOIN_TILE;
-    HF_HIP("hf_sort_perm", dev_alloc((void**)&kA, n * 8, g.stream));
-    HF_HIP("hf_sort_perm", dev_alloc((void**)&kB, n * 8, g.stream));
-    HF_HIP("hf_sort_perm", dev_alloc((void**)&iA, n * 4, g.stream));
-    HF_HIP("hf_sort_perm", dev_alloc((void**)&iB, n * 4, g.stream));
-    HF_HIP("hf_sort_perm", dev_alloc((void**)&C, L * 4, g.stream));
-    HF_HIP("hf_sort_perm", dev_alloc((void**)&CT, L * 4, g.stream));
-    HF_HIP("hf_sort_perm", dev_alloc((void**)&offs, (L + 1) * 8, g.stream));
-    HF_HIP("hf_sort_perm",
-           dev_alloc((void**)&scan_tiles, scan_tiles_n * 8, g.stream));
-    int64_t* d_total = (int64_t*)((char*)g.d_scratch + SCRATCH_NGROUPS);
+  // narrow: origin index packed under the shifted key in one u64;
+  // wide: u64 shifted keys + u32 origins, up to 8 digit passes
+  const bool wide = span >= (1ULL << 27);
+  int bits = 0;
+  while (bits < 64 && (span >> bits) != 0) ++bits;
+  const int passes = (bits + 7) / 8;
+  const int64_t ntiles = (n + SORT_TILE - 1) / SORT_TILE;
+  const int64_t L = ntiles * 256;
+  const int64_t scan_tiles_n = (L + JOIN_TILE - 1) / JOIN_TILE;
+  DevBuf kA_buf, kB_buf, iA_buf, iB_buf, C_buf, CT_buf, offs_buf, scan_buf;
+  HF_HIP("hf_sort_perm", kA_buf.alloc(n * 8));
+  HF_HIP("hf_sort_perm", kB_buf.alloc(n * 8));
+  if (wide) {
+    HF_HIP("hf_sort_perm", iA_buf.alloc(n * 4));
+    HF_HIP("hf_sort_perm", iB_buf.alloc(n * 4));
+  }
+  HF_HIP("hf_sort_perm", C_buf.alloc(L * 4));
+  HF_HIP("hf_sort_perm", CT_buf.alloc(L * 4));
+  HF_HIP("hf_sort_perm", offs_buf.alloc((L + 1) * 8));
+  HF_HIP("hf_sort_perm", scan_buf.alloc(scan_tiles_n * 8));
+  using u64 = unsigned long long;
+  u64 *kcur = kA_buf.as<u64>(), *kalt = kB_buf.as<u64>();
+  unsigned *icur = iA_buf.as<unsigned>(), *ialt = iB_buf.as<unsigned>();
+  unsigned *C = C_buf.as<unsigned>(), *CT = CT_buf.as<unsigned>();
+  u64* offs = offs_buf.as<u64>();
+  int64_t* scan_tiles = scan_buf.as<int64_t>();
+  const uint32_t wgrid =
+      (uint32_t)std::min<int64_t>((ntiles + SORT_WPB - 1) / SORT_WPB, 2048);
+  if (wide) {
     rc = timed_launch("sort_pack", [&] {
       hipLaunchKernelGGL(k_sort_pack_wide, dim3((uint32_t)grid_for(n)),
                          dim3(BLOCK), 0, g.stream, (const int64_t*)keys->dptr,
-                         n, key_min, span, ascending, kA, iA);
+                         n, key_min, span, ascending, kcur, icur);
     });
-    unsigned long long *kcur = kA, *kalt = kB;
-    unsigned *icur = iA, *ialt = iB;
-    const uint32_t wgrid =
-        (uint32_t)std::min<int64_t>((ntiles + SORT_WPB - 1) / SORT_WPB, 2048);
     for (int p = 0; p < passes && rc == HF_OK; ++p) {
       const int shift = 8 * p;
       rc = timed_launch("sort_pass", [&] {
         hipLaunchKernelGGL(k_sort_count_wide, dim3(wgrid), dim3(BLOCK), 0,
                            g.stream, kcur, n, shift, C, ntiles);
-        hipLaunchKernelGGL(k_transpose256,
-                           dim3((uint32_t)((ntiles + 31) / 32), 8), dim3(1024),
-                           0, g.stream, C, CT, ntiles);
-        hipLaunchKernelGGL(k_tile_sums_u32, dim3((uint32_t)scan_tiles_n),
-                           dim3(BLOCK), 0, g.stream, CT, L, scan_tiles);
-        hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, g.stream,
-                           scan_tiles, scan_tiles_n, d_total);
-        hipLaunchKernelGGL(k_scan_apply_u32, dim3((uint32_t)scan_tiles_n),
-                           dim3(BLOCK), 0, g.stream, CT, L, scan_tiles,
-                           d_total, offs);
+        sort_digit_offsets(C, CT, scan_tiles, offs, ntiles);
         hipLaunchKernelGGL(k_sort_scatter_wide, dim3(wgrid), dim3(BLOCK), 0,
                            g.stream, kcur, icur, n, shift, offs, ntiles, kalt,
                            ialt);
@@ -4883,79 +4925,33 @@ int hf_sort_perm(const hf_col* keys, int ascending, hf_col** out_perm) {
       rc = timed_launch("sort_unpack", [&] {
         hipLaunchKernelGGL(k_sort_unpack_wide, dim3((uint32_t)grid_for(n)),
                            dim3(BLOCK), 0, g.stream, icur, n,
-                           (int64_t*)(*out_perm)->dptr);
+                           perm.data<int64_t>());
       });
-    dev_free(kA, g.stream);
-    dev_free(kB, g.stream);
-    dev_free(iA, g.stream);
-    dev_free(iB, g.stream);
-    dev_free(C, g.stream);
-    dev_free(CT, g.stream);
-    dev_free(offs, g.stream);
-    dev_free(scan_tiles, g.stream);
-    if (rc != HF_OK) { hf_col_free(*out_perm); *out_perm = nullptr; }
-    return rc;
-  }
-  int bits = 0;
-  while ((span >> bits) != 0) ++bits;
-  const int passes = (bits + 7) / 8;
-  const int64_t ntiles = (n + SORT_TILE - 1) / SORT_TILE;
-  const int64_t L = ntiles * 256;
-  unsigned long long *bufA = nullptr, *bufB = nullptr, *offs = nullptr;
-  unsigned *C = nullptr, *CT = nullptr;
-  int64_t* scan_tiles = nullptr;
-  const int64_t scan_tiles_n = (L + JOIN_TILE - 1) / JOIN_TILE;
-  HF_HIP("hf_sort_perm", dev_alloc((void**)&bufA, n * 8, g.stream));
-  HF_HIP("hf_sort_perm", dev_alloc((void**)&bufB, n * 8, g.stream));
-  HF_HIP("hf_sort_perm", dev_alloc((void**)&C, L * 4, g.stream));
-  HF_HIP("hf_sort_perm", dev_alloc((void**)&CT, L * 4, g.stream));
-  HF_HIP("hf_sort_perm", dev_alloc((void**)&offs, (L + 1) * 8, g.stream));
-  HF_HIP("hf_sort_perm", dev_alloc((void**)&scan_tiles, scan_tiles_n * 8,
-                                   g.stream));
-  int64_t* d_total = (int64_t*)((char*)g.d_scratch + SCRATCH_NGROUPS);
-  rc = timed_launch("sort_pack", [&] {
-    hipLaunchKernelGGL(k_sort_pack, dim3((uint32_t)grid_for(n)), dim3(BLOCK),
-                       0, g.stream, (const int64_t*)keys->dptr, n, key_min,
-                       span, ascending, bufA);
-  });
-  unsigned long long* cur = bufA;
-  unsigned long long* alt = bufB;
-  const uint32_t wgrid =
-      (uint32_t)std::min<int64_t>((ntiles + SORT_WPB - 1) / SORT_WPB, 2048);
-  for (int p = 0; p < passes && rc == HF_OK; ++p) {
-    const int shift = 8 * p;
-    rc = timed_launch("sort_pass", [&] {
-      hipLaunchKernelGGL(k_sort_count, dim3(wgrid), dim3(BLOCK), 0, g.stream,
-                         cur, n, shift, C, ntiles);
-      hipLaunchKernelGGL(k_transpose256,
-                         dim3((uint32_t)((ntiles + 31) / 32), 8), dim3(1024),
-                         0, g.stream, C, CT, ntiles);
-      hipLaunchKernelGGL(k_tile_sums_u32, dim3((uint32_t)scan_tiles_n),
-                         dim3(BLOCK), 0, g.stream, CT, L, scan_tiles);
-      hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, g.stream,
-                         scan_tiles, scan_tiles_n, d_total);
-      hipLaunchKernelGGL(k_scan_apply_u32, dim3((uint32_t)scan_tiles_n),
-                         dim3(BLOCK), 0, g.stream, CT, L, scan_tiles, d_total,
-                         offs);
-      hipLaunchKernelGGL(k_sort_scatter, dim3(wgrid), dim3(BLOCK), 0, g.stream,
-                         cur, n, shift, offs, ntiles, alt);
+  } else {
+    rc = timed_launch("sort_pack", [&] {
+      hipLaunchKernelGGL(k_sort_pack, dim3((uint32_t)grid_for(n)), dim3(BLOCK),
+                         0, g.stream, (const int64_t*)keys->dptr, n, key_min,
+                         span, ascending, kcur);
     });
-    std::swap(cur, alt);
+    for (int p = 0; p < passes && rc == HF_OK; ++p) {
+      const int shift = 8 * p;
+      rc = timed_launch("sort_pass", [&] {
+        hipLaunchKernelGGL(k_sort_count, dim3(wgrid), dim3(BLOCK), 0, g.stream,
+                           kcur, n, shift, C, ntiles);
+        sort_digit_offsets(C, CT, scan_tiles, offs, ntiles);
+        hipLaunchKernelGGL(k_sort_scatter, dim3(wgrid), dim3(BLOCK), 0,
+                           g.stream, kcur, n, shift, offs, ntiles, kalt);
+      });
+      std::swap(kcur, kalt);
+    }
+    if (rc == HF_OK)
+      rc = timed_launch("sort_unpack", [&] {
+        hipLaunchKernelGGL(k_sort_unpack, dim3((uint32_t)grid_for(n)),
+                           dim3(BLOCK), 0, g.stream, kcur, n,
+                           perm.data<int64_t>());
+      });
   }
-  if (rc == HF_OK)
-    rc = timed_launch("sort_unpack", [&] {
-      hipLaunchKernelGGL(k_sort_unpack, dim3((uint32_t)grid_for(n)),
-                         dim3(BLOCK), 0, g.stream, cur,
-                         n, (int64_t*)(*out_perm)->dptr);
-    });
-  dev_free(bufA, g.stream);
-  dev_free(bufB, g.stream);
-  dev_free(C, g.stream);
-  dev_free(CT, g.stream);
-  dev_free(offs, g.stream);
-  dev_free(scan_tiles, g.stream);
-  if (rc != HF_OK) { hf_col_free(*out_perm); *out_perm = nullptr; }
-  return rc;
+  return perm.commit_if(rc, out_perm);
 }
 
 int hf_fill_f64(uintptr_t dptr, double value, int64_t n) {
@@ -4972,17 +4968,17 @@ int hf_fixup_empty(const hf_col* val, const hf_col* cnt, hf_col** out) {
   if (!val || !cnt || !out || val->len != cnt->len ||
       val->dtype != HF_FLOAT64 || cnt->dtype != HF_INT64)
     return set_err(HF_ERR_ARG, "hf_fixup_empty", "bad args");
-  int rc = hf_col_alloc(val->len, HF_FLOAT64, out);
+  ColOut o;
+  int rc = o.alloc(val->len, HF_FLOAT64);
   if (rc != HF_OK) return rc;
-  if (val->len == 0) return HF_OK;
+  if (val->len == 0) { o.commit(out); return HF_OK; }
   rc = timed_launch("fixup_empty", [&] {
     hipLaunchKernelGGL(k_fixup_empty, dim3((uint32_t)grid_for(val->len)),
                        dim3(BLOCK), 0, g.stream, (const double*)val->dptr,
-                       (const int64_t*)cnt->dptr, (double*)(*out)->dptr,
+                       (const int64_t*)cnt->dptr, o.data<double>(),
                        val->len);
   });
-  if (rc != HF_OK) { hf_col_free(*out); *out = nullptr; }
-  return rc;
+  return o.commit_if(rc, out);
 }
 
 // ---- compare + filter ----
@@ -5000,7 +4996,8 @@ int hf_compare_scalar(int op, const hf_col* col, double scalar, hf_col** out) {
   if (!col || !out) return set_err(HF_ERR_ARG, "hf_compare_scalar", "null");
   if (op < HF_CMP_GT || op > HF_CMP_NOTNA)
     return set_err(HF_ERR_ARG, "hf_compare_scalar", "unknown op");
-  int rc = hf_col_alloc(col->len, HF_INT64, out);
+  ColOut o;
+  int rc = o.alloc(col->len, HF_INT64);
   if (rc != HF_OK) return rc;
   const int64_t n = col->len;
   auto L = [&](auto opTag, auto tTag) {
@@ -5009,25 +5006,21 @@ int hf_compare_scalar(int op, const hf_col* col, double scalar, hf_col** out) {
     return timed_launch("compare", [&] {
       hipLaunchKernelGGL((k_compare<O, T>), dim3((uint32_t)grid_for(n)),
                          dim3(BLOCK), 0, g.stream, (const T*)col->dptr,
-                         (long long*)(*out)->dptr, scalar, n);
+                         o.data<long long>(), scalar, n);
     });
   };
   struct F64 { using type = double; };
   struct I64 { using type = long long; };
   const bool f = col->dtype == HF_FLOAT64;
   switch (op) {
-#define HF_CMP_CASE(O)                                                         \
-  case O:                                                                      \
-    rc = f ? L(std::integral_constant<int, O>{}, F64{})                        \
-           : L(std::integral_constant<int, O>{}, I64{});                       \
-    break;
+#define HF_CMP_CASE(O) \
+  case O: rc = f ? L(int_tag<O>{}, F64{}) : L(int_tag<O>{}, I64{}); break;
     HF_CMP_CASE(HF_CMP_GT) HF_CMP_CASE(HF_CMP_GE) HF_CMP_CASE(HF_CMP_LT)
     HF_CMP_CASE(HF_CMP_LE) HF_CMP_CASE(HF_CMP_EQ) HF_CMP_CASE(HF_CMP_NE)
     HF_CMP_CASE(HF_CMP_NOTNA)
 #undef HF_CMP_CASE
   }
-  if (rc != HF_OK) { hf_col_free(*out); *out = nullptr; }
-  return rc;
+  return o.commit_if(rc, out);
 }
 
 int hf_filter_plan(const hf_col* mask, hf_filterplan** out, int64_t* n_kept) {
@@ -5038,21 +5031,20 @@ int hf_filter_plan(const hf_col* mask, hf_filterplan** out, int64_t* n_kept) {
     return set_err(HF_ERR_ARG, "hf_filter_plan", "mask must be int64 0/1");
   const int64_t n = mask->len;
   const int64_t ntiles = n > 0 ? (n + FILT_TILE - 1) / FILT_TILE : 1;
-  hf_filterplan* p = new hf_filterplan{};
+  PlanOwner p(new hf_filterplan{}, hf_filter_plan_free);
   p->mask = (const long long*)mask->dptr;
   p->n = n;
   p->ntiles = ntiles;
-  HF_HIP("hf_filter_plan",
-         dev_alloc((void**)&p->d_tiles, ntiles * 8, g.stream));
+  HF_HIP("hf_filter_plan", DevBuf::alloc_into(p->d_tiles, ntiles * 8));
   HF_HIP("hf_filter_plan", hipMemsetAsync(p->d_tiles, 0, ntiles * 8, g.stream));
-  int64_t* d_total = (int64_t*)((char*)g.d_scratch + SCRATCH_NGROUPS);
+  int64_t* d_total = scratch_at<int64_t>(SCRATCH_NGROUPS);
   int rc = HF_OK;
   if (n > 0) {
     rc = timed_launch("filter_count", [&] {
       hipLaunchKernelGGL(k_filter_count, dim3((uint32_t)ntiles), dim3(BLOCK), 0,
                          g.stream, p->mask, n, p->d_tiles);
     });
-    if (rc != HF_OK) { hf_filter_plan_free(p); return rc; }
+    if (rc != HF_OK) return rc;
   }
   hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, g.stream,
                      p->d_tiles, ntiles, d_total);
@@ -5060,7 +5052,7 @@ int hf_filter_plan(const hf_col* mask, hf_filterplan** out, int64_t* n_kept) {
          hipMemcpyAsync(&p->total, d_total, 8, hipMemcpyDeviceToHost, g.stream));
   HF_HIP("hf_filter_plan", hipStreamSynchronize(g.stream));
   *n_kept = p->total;
-  *out = p;
+  *out = p.release();
   return HF_OK;
 }
 
@@ -5076,39 +5068,39 @@ int hf_filter_apply(const hf_filterplan* p, const hf_col* col, hf_col** out) {
   if (!p || !col || !out) return set_err(HF_ERR_ARG, "hf_filter_apply", "null");
   if (col->len != p->n)
     return set_err(HF_ERR_ARG, "hf_filter_apply", "length mismatch");
-  int rc = hf_col_alloc(p->total, col->dtype, out);
+  ColOut o;
+  int rc = o.alloc(p->total, col->dtype);
   if (rc != HF_OK) return rc;
-  if (p->n == 0 || p->total == 0) return HF_OK;
+  if (p->n == 0 || p->total == 0) { o.commit(out); return HF_OK; }
   rc = timed_launch("filter_scatter", [&] {
     if (col->dtype == HF_FLOAT64)
       hipLaunchKernelGGL((k_filter_scatter<double, false>),
                          dim3((uint32_t)p->ntiles), dim3(BLOCK), 0, g.stream,
                          p->mask, (const double*)col->dptr, p->n, p->d_tiles,
-                         (int64_t)0, (double*)(*out)->dptr);
+                         (int64_t)0, o.data<double>());
     else
       hipLaunchKernelGGL((k_filter_scatter<long long, false>),
                          dim3((uint32_t)p->ntiles), dim3(BLOCK), 0, g.stream,
                          p->mask, (const long long*)col->dptr, p->n, p->d_tiles,
-                         (int64_t)0, (long long*)(*out)->dptr);
+                         (int64_t)0, o.data<long long>());
   });
-  if (rc != HF_OK) { hf_col_free(*out); *out = nullptr; }
-  return rc;
+  return o.commit_if(rc, out);
 }
 
 int hf_filter_iota(const hf_filterplan* p, int64_t base, hf_col** out) {
   HF_NEED_INIT("hf_filter_iota");
   if (!p || !out) return set_err(HF_ERR_ARG, "hf_filter_iota", "null");
-  int rc = hf_col_alloc(p->total, HF_INT64, out);
+  ColOut o;
+  int rc = o.alloc(p->total, HF_INT64);
   if (rc != HF_OK) return rc;
-  if (p->n == 0 || p->total == 0) return HF_OK;
+  if (p->n == 0 || p->total == 0) { o.commit(out); return HF_OK; }
   rc = timed_launch("filter_iota", [&] {
     hipLaunchKernelGGL((k_filter_scatter<long long, true>),
                        dim3((uint32_t)p->ntiles), dim3(BLOCK), 0, g.stream,
                        p->mask, (const long long*)nullptr, p->n, p->d_tiles,
-                       base, (long long*)(*out)->dptr);
+                       base, o.data<long long>());
   });
-  if (rc != HF_OK) { hf_col_free(*out); *out = nullptr; }
-  return rc;
+  return o.commit_if(rc, out);
 }
 
 // ---- profiling ----

@@ -214,7 +214,13 @@ def sort_perm(keys: np.ndarray, ascending: bool = True) -> np.ndarray:
         return np.empty(0, np.int64)
     if ascending:
         return np.argsort(keys, kind="stable").astype(np.int64)
-    return np.argsort(keys.max() - keys, kind="stable").astype(np.int64)
+    if keys.dtype == np.int64:
+        # max - key modulo 2^64: a span of 2^63 or more does not fit int64
+        # (the signed difference wraps and orders negative keys first)
+        flipped = keys.max().astype(np.uint64) - keys.astype(np.uint64)
+    else:
+        flipped = keys.max() - keys
+    return np.argsort(flipped, kind="stable").astype(np.int64)
 
 
 # ---------------------------------------------------------------------------
