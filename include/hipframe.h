@@ -260,6 +260,26 @@ int hf_groupby_compact(uintptr_t sums, uintptr_t rowcnt, uintptr_t counts,
                        hf_col** out_counts,        /* nvals cols or NULL      */
                        int64_t* n_groups);
 
+/* Accumulate + compact of ONE partition in one call, for a groupby whose
+ * table needs no cross-partition or cross-GPU merge: same arguments as the
+ * accumulate (the library allocates and initialises the tables itself) and
+ * same caller-owned outputs as the compact; out_counts is filled when
+ * want_counts != 0.  Results equal the two-call path within the reduction
+ * order of floating-point sums.
+ * On the radix path the first call on a key column records, next to the
+ * scatter plan, the column's group map (present slots and compacted keys —
+ * functions of the immutable key column and (key_min, n_slots) alone); later
+ * calls with the same (key_min, n_slots) and bucket width skip the dense
+ * tables and the compaction: per value column they replay the plan, flush
+ * per-chunk partial tables with plain stores and fold them straight into the
+ * output columns, with no host synchronisation.  A column with keys outside
+ * [key_min, key_min + n_slots) never caches a map and fails on every call. */
+int hf_groupby_reduce(const hf_col* keys, const hf_col* const* vals,
+                      int nvals, int agg_op, int want_counts,
+                      int64_t key_min, int64_t n_slots,
+                      hf_col** out_keys, hf_col** out_sums,
+                      hf_col** out_counts, int64_t* n_groups);
+
 /* ---- Join: broadcast-right hash (dense-range CSR) inner join ----
  * Device form of MergeImpl.row_axis_merge
  * (modin/core/storage_formats/pandas/merge.py:104-178: materialize the right

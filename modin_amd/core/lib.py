@@ -168,6 +168,14 @@ def load() -> ct.CDLL:
                                               ct.POINTER(ct.c_void_p),
                                               ct.POINTER(ct.c_void_p),
                                               ct.POINTER(ct.c_int64)]),
+            "hf_groupby_reduce": (ct.c_int, [ct.c_void_p,
+                                             ct.POINTER(ct.c_void_p),
+                                             ct.c_int, ct.c_int, ct.c_int,
+                                             ct.c_int64, ct.c_int64,
+                                             ct.POINTER(ct.c_void_p),
+                                             ct.POINTER(ct.c_void_p),
+                                             ct.POINTER(ct.c_void_p),
+                                             ct.POINTER(ct.c_int64)]),
             "hf_col_concat": (ct.c_int, [ct.POINTER(ct.c_void_p), ct.c_int,
                                          ct.POINTER(ct.c_void_p)]),
             "hf_col_slice": (ct.c_int, [ct.c_void_p, ct.c_int64, ct.c_int64,
@@ -215,7 +223,7 @@ def exported_symbols():
         "hf_memset_raw", "hf_dev_live", "hf_map_scalar", "hf_map_scalar_i64",
         "hf_binary",
         "hf_reduce", "hf_groupby_accum", "hf_group_moments",
-        "hf_groupby_compact", "hf_fill_f64",
+        "hf_groupby_compact", "hf_groupby_reduce", "hf_fill_f64",
         "hf_fixup_empty", "hf_sort_perm", "hf_fill_i64",
         "hf_fill_randint", "hf_fill_randf64", "hf_fill_randcdf",
         "hf_groupby_hash_accum", "hf_groupby_hash_compact",
@@ -581,6 +589,37 @@ def groupby_compact(sums: int, rowcnt: int, counts: int, nvals: int,
     scols = [_wrap(ct.c_void_p(out_sums[c]), n, HF_FLOAT64) for c in range(nvals)]
     ccols = ([_wrap(ct.c_void_p(out_counts[c]), n, HF_INT64) for c in range(nvals)]
              if counts else None)
+    return kcol, scols, ccols, n
+
+
+def is_native_col(col) -> bool:
+    """True for a column that lives in the loaded, initialised native library
+    (the test suite's numpy mock never loads it and has columns of its own)."""
+    return (_dll is not None and _inited_gpu is not None
+            and isinstance(col, ColumnRef))
+
+
+def groupby_reduce(keys: ColumnRef, vals: list, agg_op: int,
+                   want_counts: bool, key_min: int, n_slots: int):
+    """Accumulate + compact of one partition in one call (hf_groupby_reduce).
+    Returns what groupby_compact returns."""
+    ensure_ready()
+    nvals = len(vals)
+    arr = (ct.c_void_p * max(nvals, 1))(*[v.handle for v in vals])
+    out_keys = ct.c_void_p()
+    out_sums = (ct.c_void_p * max(nvals, 1))()
+    out_counts = (ct.c_void_p * max(nvals, 1))()
+    n_groups = ct.c_int64(0)
+    _check(load().hf_groupby_reduce(keys.handle, arr, nvals, agg_op,
+                                    1 if want_counts else 0, key_min, n_slots,
+                                    ct.byref(out_keys), out_sums,
+                                    out_counts if want_counts else None,
+                                    ct.byref(n_groups)), "hf_groupby_reduce")
+    n = n_groups.value
+    kcol = _wrap(out_keys, n, HF_INT64)
+    scols = [_wrap(ct.c_void_p(out_sums[c]), n, HF_FLOAT64) for c in range(nvals)]
+    ccols = ([_wrap(ct.c_void_p(out_counts[c]), n, HF_INT64)
+              for c in range(nvals)] if want_counts else None)
     return kcol, scols, ccols, n
 
 

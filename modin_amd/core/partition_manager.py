@@ -272,6 +272,16 @@ class HipDataframePartitionManager:
                     agg_op)
             return k4, s4, c4, n4, biases
         n_slots = max(n_slots, 1)
+        # one non-empty partition on one rank needs no table merge: the
+        # single-call entry caches the group map on the key column
+        live = [(kcol, vals) for kcol, vals in zip(key_cols, val_cols_per_part)
+                if kcol.length]
+        if len(live) == 1 and not is_active() \
+                and lib.is_native_col(live[0][0]):
+            kcol, vals = live[0]
+            keys, sums, counts, n = lib.groupby_reduce(
+                kcol, vals, agg_op, want_counts, kmin, n_slots)
+            return keys, sums, counts, n, biases
         table = GroupbyTable(len(val_names), kmin, n_slots, want_counts,
                              agg_op)
         for kcol, vals in zip(key_cols, val_cols_per_part):

@@ -60,6 +60,8 @@ struct GbKeyCache {
   // launches copy cursors D2D and never touch the host (no H2D, no sync)
   void*   d_curinit = nullptr;   // u32[nb]
   void*   d_work = nullptr;      // GbWorkItem[work_n]
+  void*   d_item0 = nullptr;     // u32[nb + 1]: bucket -> its first work item
+                                 // (a bucket's items are contiguous)
   int64_t work_n = 0;
   int64_t radix_rows = 0;        // payload rows (64-aligned region total)
   int     radix_rl = 0;          // validity: matches (hist_kmin, hist_nb)
@@ -79,8 +81,18 @@ struct GbKeyCache {
   int64_t plan_kmin = 0;
   int64_t plan_nslots = 0;
   int     plan_rl = 0;           // 0 = no plan
+  // cached group map: which slots are present, and the compacted keys, are
+  // functions of the key column and (key_min, n_slots) alone.  Valid for
+  // exactly the plan's (plan_kmin, plan_nslots, plan_rl) and dropped with it;
+  // armed (d_gidx != null) only by a call that compacted with a valid plan
+  // and a zero error word, so a column with out-of-range keys never has one.
+  // hf_groupby_reduce then skips the dense tables and the compaction.
+  void*   d_gidx = nullptr;      // u32[plan_nslots]: slot -> output row,
+                                 // 0xFFFFFFFF = absent
+  void*   d_gkeys = nullptr;     // i64[n_groups]: compacted ascending keys
+  int64_t n_groups = 0;
 
-  void drop_plan();     // free the plan buffers, plan_rl = 0
+  void drop_plan();     // free the plan and group-map buffers, plan_rl = 0
   void drop_derived();  // the histogram changed: drop the layout and the plan
   void release();       // the column dies: give every device block back
 };
@@ -408,11 +420,15 @@ void GbKeyCache::drop_plan() {
   drop_dev(d_plan_tab);
   drop_dev(d_plan_meta);
   plan_rl = 0;
+  drop_dev(d_gidx);
+  drop_dev(d_gkeys);
+  n_groups = 0;
 }
 
 void GbKeyCache::drop_derived() {
   drop_dev(d_curinit);
   drop_dev(d_work);
+  drop_dev(d_item0);
   work_n = radix_rows = 0;
   radix_rl = 0;
   drop_plan();
@@ -850,7 +866,11 @@ __global__ void __launch_bounds__(BLOCK) k_gb_accum(
 //   P2 k_gb_bucket_agg : stream each bucket chunk into an LDS table
 //                        (ds_add_f64 behind a register run-accumulator for
 //                        skewed keys), merge non-empty slots into the
-//                        global dense table (atomics only per slot)
+//                        global dense table (atomics only per slot) — or,
+//                        for hf_groupby_reduce on a cached group map, store
+//                        the whole table as one partial row (PART), which
+//      k_gb_combine    : folds per slot, in work-item order, straight into
+//                        the compacted output (no dense table, no atomics)
 // n_slots <= GB_RANGE skips P0/P1 entirely (k_gb_dense: one 16 B/row pass).
 // ---------------------------------------------------------------------------
 
@@ -1223,27 +1243,36 @@ __global__ void k_gb_plan_err(const unsigned long long* __restrict__ meta,
 // region base + k * AGG_CHUNK, regions are 64-row aligned and AGG_CHUNK is
 // even (ensure_radix_layout) — so the ushort2/double2 streams are aligned
 // from the first row; only the last chunk of a bucket can have an odd tail.
-template <bool ROWCNT, bool CNT, bool HAVE_VAL, int RL, int AOP>
+// PART (hf_groupby_reduce on a cached group map): presence is already known,
+// so no touch bytes and no ROWCNT, and instead of the atomic merge the block
+// stores its whole table — identity in untouched slots — as row blockIdx.x of
+// part_sums / part_cnt with plain 16-byte stores; k_gb_combine folds the rows
+// of a bucket.
+template <bool ROWCNT, bool CNT, bool HAVE_VAL, int RL, int AOP,
+          bool PART = false>
 __global__ void __launch_bounds__(512) k_gb_bucket_agg(
     const double* __restrict__ vals, const unsigned short* __restrict__ lowkeys,
     const GbWorkItem* __restrict__ work, int64_t n_slots,
     double* __restrict__ gsums, unsigned long long* __restrict__ growcnt,
-    unsigned long long* __restrict__ gcounts) {
+    unsigned long long* __restrict__ gcounts,
+    double* __restrict__ part_sums = nullptr,   // [gridDim.x][RANGE] (PART)
+    unsigned* __restrict__ part_cnt = nullptr) {  // likewise, with CNT
+  static_assert(!PART || (HAVE_VAL && !ROWCNT), "PART flushes value tables");
   constexpr int RANGE = 1 << RL;
-  __shared__ double lsums[HAVE_VAL ? RANGE : 1];
-  __shared__ unsigned lcnt[CNT ? RANGE : 1];
-  __shared__ unsigned char ltouch[RANGE];
+  __shared__ __attribute__((aligned(16))) double lsums[HAVE_VAL ? RANGE : 1];
+  __shared__ __attribute__((aligned(16))) unsigned lcnt[CNT ? RANGE : 1];
+  __shared__ unsigned char ltouch[PART ? 1 : RANGE];
   const GbWorkItem w = work[blockIdx.x];
   for (int s = threadIdx.x; s < RANGE; s += blockDim.x) {
     if (HAVE_VAL) lsums[s] = agg_identity<AOP>();
-    ltouch[s] = 0;
+    if (!PART) ltouch[s] = 0;
     if (CNT) lcnt[s] = 0;
   }
   __syncthreads();
   const int64_t end = w.start + w.len;
   auto one_row = [&](int64_t i) {
     const int slot = lowkeys[i];
-    ltouch[slot] = 1;
+    if (!PART) ltouch[slot] = 1;
     if (HAVE_VAL) {
       const double v = vals[i];
       if (v == v) {
@@ -1273,7 +1302,7 @@ __global__ void __launch_bounds__(512) k_gb_bucket_agg(
     rcnt = 0;
   };
   auto feed = [&](int slot, double v) {
-    ltouch[slot] = 1;
+    if (!PART) ltouch[slot] = 1;
     if (HAVE_VAL && v == v) {
       if (slot == rslot) {
         racc = AOP == HF_AGG_SUM ? racc + v
@@ -1301,6 +1330,19 @@ __global__ void __launch_bounds__(512) k_gb_bucket_agg(
   flush();
   if (((end - a0) & 1) && threadIdx.x == 0) one_row(end - 1);
   __syncthreads();
+  if (PART) {
+    double2* ps = reinterpret_cast<double2*>(part_sums +
+                                             (int64_t)blockIdx.x * RANGE);
+    const double2* ls = reinterpret_cast<const double2*>(lsums);
+    for (int s = threadIdx.x; s < RANGE / 2; s += blockDim.x) ps[s] = ls[s];
+    if (CNT) {
+      uint4* pc = reinterpret_cast<uint4*>(part_cnt +
+                                           (int64_t)blockIdx.x * RANGE);
+      const uint4* lc = reinterpret_cast<const uint4*>(lcnt);
+      for (int s = threadIdx.x; s < RANGE / 4; s += blockDim.x) pc[s] = lc[s];
+    }
+    return;
+  }
   const int64_t gbase = (int64_t)w.bucket << RL;
   for (int s = threadIdx.x; s < RANGE; s += blockDim.x) {
     if (!ltouch[s] || gbase + s >= n_slots) continue;
@@ -1308,6 +1350,56 @@ __global__ void __launch_bounds__(512) k_gb_bucket_agg(
     if (ROWCNT) atomicAdd(&growcnt[gbase + s], 1ULL);
     if (CNT) atomicAdd(&gcounts[gbase + s], (unsigned long long)lcnt[s]);
   }
+}
+
+// Merge + compaction of the PART flush, one thread per slot: fold the partial
+// tables of the slot's bucket in work-item order (so the chunk merge is
+// deterministic) and write the result at the slot's cached output row.
+// Absent slots are skipped; a present slot's bucket has at least one item.
+template <int RL, int AOP, bool CNT>
+__global__ void __launch_bounds__(BLOCK) k_gb_combine(
+    const unsigned* __restrict__ gidx, const unsigned* __restrict__ item0,
+    const double* __restrict__ part_sums, const unsigned* __restrict__ part_cnt,
+    int64_t n_slots, double* __restrict__ out_sums,
+    int64_t* __restrict__ out_counts) {
+  constexpr int RANGE = 1 << RL;
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n_slots) return;
+  const unsigned gi = gidx[s];
+  if (gi == 0xFFFFFFFFu) return;
+  const int64_t b = s >> RL;
+  const int64_t lo = s & (RANGE - 1);
+  double acc = agg_identity<AOP>();
+  int64_t cnt = 0;
+  auto fold = [&](double p) {
+    acc = AOP == HF_AGG_SUM ? acc + p
+          : AOP == HF_AGG_MIN ? fmin(acc, p) : fmax(acc, p);
+  };
+  const unsigned i1 = item0[b + 1];
+  unsigned i = item0[b];
+  // a skewed head bucket has hundreds of items and only RANGE threads to fold
+  // them: load U tables' values at once, then fold them in item order
+  constexpr unsigned U = 8;
+  for (; i + U <= i1; i += U) {
+    double p[U];
+    unsigned c[U];
+#pragma unroll
+    for (unsigned u = 0; u < U; ++u) {
+      p[u] = part_sums[(int64_t)(i + u) * RANGE + lo];
+      if (CNT) c[u] = part_cnt[(int64_t)(i + u) * RANGE + lo];
+    }
+#pragma unroll
+    for (unsigned u = 0; u < U; ++u) {
+      fold(p[u]);
+      if (CNT) cnt += c[u];
+    }
+  }
+  for (; i < i1; ++i) {
+    fold(part_sums[(int64_t)i * RANGE + lo]);
+    if (CNT) cnt += part_cnt[(int64_t)i * RANGE + lo];
+  }
+  out_sums[gi] = acc;
+  if (CNT) out_counts[gi] = cnt;
 }
 
 // Dense direct path: n_slots <= GB_RANGE, one 16 B/row pass per column.
@@ -1725,6 +1817,40 @@ __global__ void __launch_bounds__(BLOCK) k_compact_scatter(
         if (COUNTS) out_counts[c][pos] = (int64_t)counts[(int64_t)c * n_slots + s];
       }
     }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int64_t tot = 0;
+      for (int w = 0; w < BLOCK / 64; ++w) tot += s_wave_cnt[w];
+      s_base += tot;
+    }
+    __syncthreads();
+  }
+}
+
+// The group map of a compaction (GbKeyCache::d_gidx): slot -> output row with
+// the ranking of k_compact_scatter, 0xFFFFFFFF for absent slots.
+__global__ void __launch_bounds__(BLOCK) k_gb_gidx(
+    const unsigned long long* __restrict__ rowcnt, int64_t n_slots,
+    const int64_t* __restrict__ tile_offsets, unsigned* __restrict__ gidx) {
+  const int64_t t0 = (int64_t)blockIdx.x * COMPACT_TILE;
+  const int64_t t1 = min(t0 + (int64_t)COMPACT_TILE, n_slots);
+  __shared__ int64_t s_base;
+  __shared__ int s_wave_cnt[BLOCK / 64];
+  if (threadIdx.x == 0) s_base = tile_offsets[blockIdx.x];
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int64_t chunk = t0; chunk < t1; chunk += blockDim.x) {
+    const int64_t s = chunk + threadIdx.x;
+    const bool pred = (s < t1) && (rowcnt[s] != 0);
+    const uint64_t ballot = __ballot(pred);
+    if (lane == 0) s_wave_cnt[wave] = __popcll(ballot);
+    __syncthreads();
+    int64_t wave_base = 0;
+    for (int w = 0; w < wave; ++w) wave_base += s_wave_cnt[w];
+    if (s < t1)
+      gidx[s] = pred ? (unsigned)(s_base + wave_base +
+                                  __popcll(ballot & ((1ULL << lane) - 1)))
+                     : 0xFFFFFFFFu;
     __syncthreads();
     if (threadIdx.x == 0) {
       int64_t tot = 0;
@@ -3458,9 +3584,11 @@ int ensure_radix_layout(hf_col* keys, int64_t nb) {
   kc.drop_derived();
   std::vector<unsigned> cur_init((size_t)nb);
   std::vector<GbWorkItem> work;
+  std::vector<unsigned> item0((size_t)nb + 1);
   int64_t off = 0;
   for (int64_t b = 0; b < nb; ++b) {
     cur_init[b] = (unsigned)off;
+    item0[b] = (unsigned)work.size();
     const int64_t rows_b = kc.hist[b];
     int64_t done = 0;
     while (done < rows_b) {
@@ -3470,11 +3598,16 @@ int ensure_radix_layout(hf_col* keys, int64_t nb) {
     }
     off += (rows_b + 63) & ~63LL;
   }
+  item0[nb] = (unsigned)work.size();
   if (off > 0xFFFFFFF0LL)
     return set_err(HF_ERR_UNSUPPORTED, "hf_groupby_accum",
                    "partition too large for radix scatter (shard it)");
-  DevBuf d_curinit, d_work;
+  DevBuf d_curinit, d_work, d_item0;
   HF_HIP("gb_radix", d_curinit.alloc(nb * 4));
+  HF_HIP("gb_radix", d_item0.alloc((nb + 1) * 4));
+  HF_HIP("gb_radix", hipMemcpyAsync(d_item0.as<void>(), item0.data(),
+                                    (nb + 1) * 4, hipMemcpyHostToDevice,
+                                    g.stream));
   HF_HIP("gb_radix",
          d_work.alloc(std::max<size_t>(work.size(), 1) * sizeof(GbWorkItem)));
   HF_HIP("gb_radix", hipMemcpyAsync(d_curinit.as<void>(), cur_init.data(),
@@ -3487,6 +3620,7 @@ int ensure_radix_layout(hf_col* keys, int64_t nb) {
   HF_HIP("gb_radix", hipStreamSynchronize(g.stream));
   kc.d_curinit = d_curinit.release();
   kc.d_work = d_work.release();
+  kc.d_item0 = d_item0.release();
   kc.work_n = (int64_t)work.size();
   kc.radix_rows = off;
   kc.radix_rl = RL;
@@ -3639,6 +3773,79 @@ int radix_agg(const GbRadixCall& a, const double* v, double* gs,
   });
 }
 
+// Bucket width (log2) of the radix path for a key range, 0 = range too wide.
+// Sum-only uses 8192-key buckets (bigger scatter chunks; the u8-touch agg
+// table still fits 2 blocks/CU); count/mean use 4096 (3 blocks/CU with the
+// counts table).
+int gb_radix_rl(int64_t n_slots, bool want_cnt) {
+  const int64_t nb13 = (n_slots + (1 << 13) - 1) >> 13;
+  const int64_t nb12 = (n_slots + (1 << 12) - 1) >> 12;
+  return (!want_cnt && nb13 <= GB_MAX_BUCKETS) ? 13
+         : (want_cnt && nb12 <= GB_MAX_BUCKETS) ? 12
+         : (nb13 <= GB_MAX_BUCKETS) ? 13 : 0;
+}
+
+// The steady state of hf_groupby_reduce on a column whose plan is recorded
+// and whose group map is armed: per value column replay -> P2 with the
+// partial-table flush -> combine straight into the output column.  No dense
+// tables, no memsets, no compaction count/scan, no D2H copy, no sync.  The
+// caller has checked that the plan matches (RL, key_min, n_slots); an armed
+// map implies a zero recorded out-of-range count, so the error word is not
+// touched.
+template <int RL, int AOP>
+int gb_radix_mapped(hf_col* keys, const GbPtrs& ptrs, int nvals,
+                    int64_t key_min, int64_t n_slots, bool want_counts,
+                    GroupOut& o) {
+  const GbKeyCache& kc = keys->gb;
+  const int64_t ng = kc.n_groups;
+  int rc = o.keys.alloc(ng, HF_INT64);
+  if (rc != HF_OK) return rc;
+  if (ng > 0)
+    HF_HIP("hf_groupby_reduce",
+           hipMemcpyAsync(o.keys.data<void>(), kc.d_gkeys, ng * 8,
+                          hipMemcpyDeviceToDevice, g.stream));
+  if (nvals == 0) return HF_OK;
+  constexpr int64_t RANGE = 1 << RL;
+  const int64_t nb = (n_slots + RANGE - 1) >> RL;
+  // one partial buffer serves every value column in turn, like r0
+  DevBuf r0, part_sums, part_cnt;
+  HF_HIP("hf_groupby_reduce", r0.alloc(radix_alloc_rows(kc) * 8));
+  HF_HIP("hf_groupby_reduce", part_sums.alloc(kc.work_n * RANGE * 8));
+  if (want_counts)
+    HF_HIP("hf_groupby_reduce", part_cnt.alloc(kc.work_n * RANGE * 4));
+  const GbRadixCall a{keys, nb, key_min, n_slots, nullptr, r0.as<double>(),
+                      nullptr, (unsigned short*)kc.d_plan_rk, nullptr};
+  for (int c = 0; c < nvals; ++c) {
+    rc = o.sums[c].alloc(ng, HF_FLOAT64);
+    if (rc == HF_OK && want_counts) rc = o.cnts[c].alloc(ng, HF_INT64);
+    if (rc == HF_OK) rc = radix_replay(a, ptrs.vals[c], false);
+    if (rc != HF_OK) return rc;
+    rc = with_bool(want_counts, [&](auto cTag) {
+      constexpr bool C = decltype(cTag)::value;
+      int r = timed_launch("gb_bucket_agg", [&] {
+        hipLaunchKernelGGL(
+            (k_gb_bucket_agg<false, C, true, RL, AOP, true>),
+            dim3((uint32_t)kc.work_n), dim3(512), 0, g.stream, a.r0, a.rk,
+            (const GbWorkItem*)kc.d_work, n_slots, nullptr, nullptr, nullptr,
+            part_sums.as<double>(), part_cnt.as<unsigned>());
+      });
+      if (r != HF_OK) return r;
+      // the compaction of this path, so it keeps that stat name
+      return timed_launch("gb_compact_scatter", [&] {
+        hipLaunchKernelGGL(
+            (k_gb_combine<RL, AOP, C>),
+            dim3((uint32_t)((n_slots + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0,
+            g.stream, (const unsigned*)kc.d_gidx, (const unsigned*)kc.d_item0,
+            part_sums.as<double>(), part_cnt.as<unsigned>(), n_slots,
+            o.sums[c].data<double>(),
+            C ? o.cnts[c].data<int64_t>() : nullptr);
+      });
+    });
+    if (rc != HF_OK) return rc;
+  }
+  return HF_OK;
+}
+
 // The radix groupby driver: layout -> plan mode -> P1 -> per column
 // (replay?) -> P2.  Every temporary is scoped, so any early return gives its
 // blocks back to the allocator.
@@ -3743,15 +3950,7 @@ int hf_groupby_accum(const hf_col* keys, const hf_col* const* vals, int nvals,
     if (n > 0 && n_slots <= GB_DENSE_MAX)
       return gb_dense_path<AOP>(keys, ptrs, nvals, key_min, n_slots, sums,
                                 rowcnt, counts, d_err);
-    // sum-only uses 8192-key buckets (bigger scatter chunks; the u8-touch agg
-    // table still fits 2 blocks/CU); count/mean use 4096 (3 blocks/CU with
-    // the counts table)
-    const bool want_cnt = counts != 0;
-    const int64_t nb13 = (n_slots + (1 << 13) - 1) >> 13;
-    const int64_t nb12 = (n_slots + (1 << 12) - 1) >> 12;
-    const int rl_ok = (!want_cnt && nb13 <= GB_MAX_BUCKETS) ? 13
-                      : (want_cnt && nb12 <= GB_MAX_BUCKETS) ? 12
-                      : (nb13 <= GB_MAX_BUCKETS) ? 13 : 0;
+    const int rl_ok = gb_radix_rl(n_slots, counts != 0);
     if (n > 0 && rl_ok) {
       // wide frames run the radix path in chunks of 2 value columns
       // (re-reading keys per chunk still beats the atomic fallback ~5x)
@@ -3853,10 +4052,13 @@ int hf_group_moments(const hf_col* gid, const hf_col* val, uintptr_t centre,
   return HF_OK;
 }
 
-int hf_groupby_compact(uintptr_t sums, uintptr_t rowcnt, uintptr_t counts,
-                       int nvals, int64_t key_min, int64_t n_slots,
-                       hf_col** out_keys, hf_col** out_sums, hf_col** out_counts,
-                       int64_t* n_groups) {
+// The body of hf_groupby_compact.  gidx (u32[n_slots], may be null) also
+// receives the group map of this compaction: slot -> output row, from the
+// rowcnt table and tile offsets at hand.
+static int gb_compact(uintptr_t sums, uintptr_t rowcnt, uintptr_t counts,
+                      int nvals, int64_t key_min, int64_t n_slots,
+                      hf_col** out_keys, hf_col** out_sums,
+                      hf_col** out_counts, int64_t* n_groups, unsigned* gidx) {
   HF_NEED_INIT("hf_groupby_compact");
   if (!rowcnt || nvals < 0 || nvals > GB_MAX_VALS || !out_keys || !n_groups)
     return set_err(HF_ERR_ARG, "hf_groupby_compact", "bad args");
@@ -3936,8 +4138,117 @@ int hf_groupby_compact(uintptr_t sums, uintptr_t rowcnt, uintptr_t counts,
     });
   });
   if (rc != HF_OK) return rc;
+  if (gidx) {
+    rc = timed_launch("gb_gidx", [&] {
+      hipLaunchKernelGGL(k_gb_gidx, dim3((uint32_t)ntiles), dim3(BLOCK), 0,
+                         g.stream, (const unsigned long long*)rowcnt, n_slots,
+                         d_tiles, gidx);
+    });
+    if (rc != HF_OK) return rc;
+  }
   o.commit(out_keys, out_sums, out_counts);
   *n_groups = total;
+  return HF_OK;
+}
+
+int hf_groupby_compact(uintptr_t sums, uintptr_t rowcnt, uintptr_t counts,
+                       int nvals, int64_t key_min, int64_t n_slots,
+                       hf_col** out_keys, hf_col** out_sums, hf_col** out_counts,
+                       int64_t* n_groups) {
+  return gb_compact(sums, rowcnt, counts, nvals, key_min, n_slots, out_keys,
+                    out_sums, out_counts, n_groups, nullptr);
+}
+
+int hf_groupby_reduce(const hf_col* keys, const hf_col* const* vals, int nvals,
+                      int agg_op, int want_counts, int64_t key_min,
+                      int64_t n_slots, hf_col** out_keys, hf_col** out_sums,
+                      hf_col** out_counts, int64_t* n_groups) {
+  HF_NEED_INIT("hf_groupby_reduce");
+  if (!keys || !vals || nvals < 0 || nvals > GB_MAX_VALS || !out_keys ||
+      !n_groups || (nvals > 0 && !out_sums) || (want_counts && !out_counts))
+    return set_err(HF_ERR_ARG, "hf_groupby_reduce", "bad args (nvals<=8)");
+  if (agg_op < HF_AGG_SUM || agg_op > HF_AGG_MAX)
+    return set_err(HF_ERR_ARG, "hf_groupby_reduce", "bad agg_op");
+  if (keys->dtype != HF_INT64)
+    return set_err(HF_ERR_ARG, "hf_groupby_reduce", "keys must be int64");
+  if (n_slots <= 0)
+    return set_err(HF_ERR_ARG, "hf_groupby_reduce", "n_slots<=0");
+  GbPtrs ptrs{};
+  for (int c = 0; c < nvals; ++c) {
+    if (!vals[c] || vals[c]->dtype != HF_FLOAT64 || vals[c]->len != keys->len)
+      return set_err(HF_ERR_ARG, "hf_groupby_reduce",
+                     "vals must be float64 columns of keys' length");
+    ptrs.vals[c] = (const double*)vals[c]->dptr;
+  }
+  hf_col* kcol = const_cast<hf_col*>(keys);
+  GbKeyCache& kc = kcol->gb;
+  const bool cnt = want_counts != 0;
+  // the route hf_groupby_accum takes for this call, and the plan it would find
+  const int rl = (keys->len > 0 && n_slots > GB_DENSE_MAX)
+                     ? gb_radix_rl(n_slots, cnt) : 0;
+  const bool plan_ok = rl != 0 && kc.plan_rl == rl &&
+                       kc.plan_kmin == key_min && kc.plan_nslots == n_slots;
+  if (plan_ok && kc.d_gidx) {
+    GroupOut o(nvals, cnt);
+    const int rc = with_aop(agg_op, [&](auto aopTag) {
+      return with_bool(rl == 13, [&](auto rlTag) {
+        return gb_radix_mapped<decltype(rlTag)::value ? 13 : 12,
+                               decltype(aopTag)::value>(
+            kcol, ptrs, nvals, key_min, n_slots, cnt, o);
+      });
+    });
+    if (rc != HF_OK) return rc;
+    o.commit(out_keys, out_sums, out_counts);
+    *n_groups = kc.n_groups;
+    return HF_OK;
+  }
+  // every other case: dense tables of this call's own, then the two-call path
+  const int64_t tab = (int64_t)(nvals ? nvals : 1) * n_slots;
+  DevBuf sums, rowcnt, counts, gidx;
+  HF_HIP("hf_groupby_reduce", sums.alloc(tab * 8));
+  HF_HIP("hf_groupby_reduce", rowcnt.alloc(n_slots * 8));
+  if (cnt) HF_HIP("hf_groupby_reduce", counts.alloc(tab * 8));
+  int rc = HF_OK;
+  if (agg_op == HF_AGG_SUM)
+    HF_HIP("hf_groupby_reduce",
+           hipMemsetAsync(sums.as<void>(), 0, tab * 8, g.stream));
+  else
+    rc = hf_fill_f64((uintptr_t)sums.as<void>(),
+                     agg_op == HF_AGG_MIN ? INFINITY : -INFINITY, tab);
+  if (rc != HF_OK) return rc;
+  HF_HIP("hf_groupby_reduce",
+         hipMemsetAsync(rowcnt.as<void>(), 0, n_slots * 8, g.stream));
+  if (cnt)
+    HF_HIP("hf_groupby_reduce",
+           hipMemsetAsync(counts.as<void>(), 0, tab * 8, g.stream));
+  rc = hf_groupby_accum(keys, vals, nvals, agg_op, key_min, n_slots,
+                        (uintptr_t)sums.as<void>(),
+                        (uintptr_t)rowcnt.as<void>(),
+                        (uintptr_t)counts.as<void>());
+  if (rc != HF_OK) return rc;
+  // arm the group map when this call ran on a valid recorded plan; a failed
+  // map allocation only leaves the column on this path
+  const bool arm = rl != 0 && kc.plan_rl == rl && kc.plan_kmin == key_min &&
+                   kc.plan_nslots == n_slots && kc.work_n > 0 && !kc.d_gidx;
+  if (arm && gidx.alloc(n_slots * 4) != hipSuccess) (void)hipGetLastError();
+  hf_col* okeys = nullptr;
+  rc = gb_compact((uintptr_t)sums.as<void>(), (uintptr_t)rowcnt.as<void>(),
+                  (uintptr_t)counts.as<void>(), nvals, key_min, n_slots,
+                  &okeys, out_sums, out_counts, n_groups, gidx.as<unsigned>());
+  if (rc != HF_OK) return rc;  // a nonzero error word lands here: never armed
+  *out_keys = okeys;
+  if (gidx.as<void>() && *n_groups > 0) {
+    DevBuf gkeys;
+    if (gkeys.alloc(*n_groups * 8) != hipSuccess) {
+      (void)hipGetLastError();
+    } else if (hipMemcpyAsync(gkeys.as<void>(), okeys->dptr, *n_groups * 8,
+                              hipMemcpyDeviceToDevice, g.stream) ==
+               hipSuccess) {
+      kc.d_gidx = gidx.release();
+      kc.d_gkeys = gkeys.release();
+      kc.n_groups = *n_groups;
+    }
+  }
   return HF_OK;
 }
 
