@@ -378,7 +378,9 @@ int hf_ordered_i64(const hf_col* col, int direction, hf_col** out);
  * axis=0; agg_op = HF_AGG_SUM/MIN/MAX): f64 skips NaN (NaN rows stay NaN,
  * later results unaffected), int64 is exact.  Device three-phase scan:
  * per-tile combine -> single-workgroup exclusive tile scan -> per-tile
- * apply. */
+ * apply.  f64 HF_AGG_SUM is within 48 * 2^-53 * cumsum|x| of the exact
+ * sum; f64 HF_AGG_PROD (here and in hf_seg_cumsum) carries a double-double
+ * state and is within a few 2^-53 relative. */
 int hf_cumsum(const hf_col* col, int agg_op, hf_col** out);
 
 /* SEGMENTED inclusive prefix scan: restart at every row whose `heads` entry

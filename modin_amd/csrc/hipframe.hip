@@ -2470,66 +2470,121 @@ __device__ __forceinline__ T cs_load(const T* p_, int64_t i) {
   return (v != v) ? cs_ident<T, OP>() : v;  // NaN skipped (f64)
 }
 
+// Scan STATE.  Every op carries a plain T except the f64 product, which
+// carries the running product as an unevaluated sum hi + lo (double-double).
+// A rounded product hands the relative errors of both operands on in full,
+// so a plain f64 prefix of k factors holds all k-1 roundings of its tree
+// (measured 1.9e-11 at 4.2M rows of factors near 1, where every thread run
+// restarts at exactly 1 and the roundings do not average out); with the
+// error term kept, each combine costs ~u^2 and the output rounds once.
+struct cs_dd { double hi, lo; };
+template <typename T, int OP> struct cs_state { using type = T; };
+template <> struct cs_state<double, HF_AGG_PROD> { using type = cs_dd; };
+
+__device__ __forceinline__ cs_dd cs_dd_mul(cs_dd a, cs_dd b) {
+  // no contraction here: fusing p's multiply into `p + lo` below would add
+  // the error term e a second time
+#pragma clang fp contract(off)
+  const double p = a.hi * b.hi;
+  // after overflow, at zero and on NaN there is no error term to keep: the
+  // state stays the plain product's inf / 0 / NaN
+  if (!(fabs(p) < __builtin_huge_val()) || p == 0.0) return cs_dd{p, 0.0};
+  const double e = __builtin_fma(a.hi, b.hi, -p);  // exact: a.hi*b.hi - p
+  const double lo = e + (a.hi * b.lo + a.lo * b.hi);
+  const double hi = p + lo;
+  return cs_dd{hi, lo - (hi - p)};
+}
+template <typename T, int OP, typename S = typename cs_state<T, OP>::type>
+__device__ __forceinline__ S cs_lift(T v) {
+  if constexpr (std::is_same<S, cs_dd>::value) return cs_dd{v, 0.0};
+  else return v;
+}
+template <typename T, int OP, typename S = typename cs_state<T, OP>::type>
+__device__ __forceinline__ S cs_sident() {
+  return cs_lift<T, OP>(cs_ident<T, OP>());
+}
+template <typename T, int OP, typename S = typename cs_state<T, OP>::type>
+__device__ __forceinline__ S cs_scomb(S a, S b) {
+  if constexpr (std::is_same<S, cs_dd>::value) return cs_dd_mul(a, b);
+  else return cs_comb<T, OP>(a, b);
+}
+template <typename T, int OP, typename S = typename cs_state<T, OP>::type>
+__device__ __forceinline__ T cs_value(S s) {
+  if constexpr (std::is_same<S, cs_dd>::value) return s.hi + s.lo;
+  else return s;
+}
+template <typename S>
+__device__ __forceinline__ S cs_shfl_down(S v, int off) {
+  if constexpr (std::is_same<S, cs_dd>::value)
+    return cs_dd{__shfl_down(v.hi, off), __shfl_down(v.lo, off)};
+  else return (S)__shfl_down(v, off);
+}
+
 template <typename T, int OP>
 __global__ void __launch_bounds__(BLOCK) k_cumsum_tiles(
-    const T* __restrict__ in, int64_t n, T* __restrict__ tile_sums) {
+    const T* __restrict__ in, int64_t n,
+    typename cs_state<T, OP>::type* __restrict__ tile_sums) {
+  using S = typename cs_state<T, OP>::type;
   const int64_t t0 = (int64_t)blockIdx.x * FILT_TILE;
   const int64_t t1 = min(t0 + (int64_t)FILT_TILE, n);
-  T local = cs_ident<T, OP>();
+  S local = cs_sident<T, OP>();
   for (int64_t i = t0 + threadIdx.x; i < t1; i += blockDim.x)
-    local = cs_comb<T, OP>(local, cs_load<T, OP>(in, i));
-  __shared__ T sc[BLOCK / 64];
+    local = cs_scomb<T, OP>(local, cs_lift<T, OP>(cs_load<T, OP>(in, i)));
+  __shared__ S sc[BLOCK / 64];
   for (int off = 32; off > 0; off >>= 1)
-    local = cs_comb<T, OP>(local, (T)__shfl_down(local, off));
+    local = cs_scomb<T, OP>(local, cs_shfl_down(local, off));
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) sc[wave] = local;
   __syncthreads();
   if (threadIdx.x == 0) {
-    T tot = cs_ident<T, OP>();
-    for (int w = 0; w < BLOCK / 64; ++w) tot = cs_comb<T, OP>(tot, sc[w]);
+    S tot = cs_sident<T, OP>();
+    for (int w = 0; w < BLOCK / 64; ++w) tot = cs_scomb<T, OP>(tot, sc[w]);
     tile_sums[blockIdx.x] = tot;
   }
 }
 
 template <typename T, int OP>
 __global__ void __launch_bounds__(1024) k_cumsum_scan_tiles(
-    T* __restrict__ tile_sums, int64_t ntiles) {
+    typename cs_state<T, OP>::type* __restrict__ tile_sums, int64_t ntiles) {
+  using S = typename cs_state<T, OP>::type;
   // exclusive scan under cs_comb: track each element's PREFIX (exclusive)
   // explicitly since min/max have no inverse
-  __shared__ T carry;
-  if (threadIdx.x == 0) carry = cs_ident<T, OP>();
+  __shared__ S carry;
+  if (threadIdx.x == 0) carry = cs_sident<T, OP>();
   __syncthreads();
-  __shared__ T buf[1024];
+  __shared__ S buf[1024];
   for (int64_t base = 0; base < ntiles; base += 1024) {
     const int64_t i = base + threadIdx.x;
-    T v = (i < ntiles) ? tile_sums[i] : cs_ident<T, OP>();
+    S v = (i < ntiles) ? tile_sums[i] : cs_sident<T, OP>();
     buf[threadIdx.x] = v;
     __syncthreads();
-    T excl = cs_ident<T, OP>();
+    S excl = cs_sident<T, OP>();
     for (int off = 1; off < 1024; off <<= 1) {
-      T add = (threadIdx.x >= off) ? buf[threadIdx.x - off]
-                                   : cs_ident<T, OP>();
+      S add = (threadIdx.x >= off) ? buf[threadIdx.x - off]
+                                   : cs_sident<T, OP>();
       __syncthreads();
-      buf[threadIdx.x] = cs_comb<T, OP>(buf[threadIdx.x], add);
+      buf[threadIdx.x] = cs_scomb<T, OP>(buf[threadIdx.x], add);
       __syncthreads();
     }
-    const T incl = buf[threadIdx.x];
+    const S incl = buf[threadIdx.x];
     __syncthreads();
     buf[threadIdx.x] = incl;  // reuse buf to read neighbor inclusives
     __syncthreads();
     // exclusive = inclusive of the previous lane (or identity at lane 0)
-    excl = (threadIdx.x == 0) ? cs_ident<T, OP>() : buf[threadIdx.x - 1];
-    if (i < ntiles) tile_sums[i] = cs_comb<T, OP>(carry, excl);
+    excl = (threadIdx.x == 0) ? cs_sident<T, OP>() : buf[threadIdx.x - 1];
+    if (i < ntiles) tile_sums[i] = cs_scomb<T, OP>(carry, excl);
     __syncthreads();
-    if (threadIdx.x == 1023) carry = cs_comb<T, OP>(carry, incl);
+    if (threadIdx.x == 1023) carry = cs_scomb<T, OP>(carry, incl);
     __syncthreads();
   }
 }
 
 template <typename T, int OP>
 __global__ void __launch_bounds__(BLOCK) k_cumsum_apply(
-    const T* __restrict__ in, int64_t n, const T* __restrict__ tile_base,
+    const T* __restrict__ in, int64_t n,
+    const typename cs_state<T, OP>::type* __restrict__ tile_base,
     T* __restrict__ out) {
+  using S = typename cs_state<T, OP>::type;
   const int64_t t0 = (int64_t)blockIdx.x * FILT_TILE;
   const int64_t t1 = min(t0 + (int64_t)FILT_TILE, n);
   constexpr int PER = FILT_TILE / BLOCK;  // elems per thread
@@ -2543,38 +2598,40 @@ __global__ void __launch_bounds__(BLOCK) k_cumsum_apply(
   __syncthreads();
   const int s0 = threadIdx.x * PER;
   const int lim = (int)(t1 - t0);
-  T loc[PER];
-  T run = cs_ident<T, OP>();
+  S loc[PER];
+  S run = cs_sident<T, OP>();
   for (int j = 0; j < PER; ++j) {
     if (s0 + j < lim) {
       const T v = stage[s0 + j];
-      run = cs_comb<T, OP>(run, (v != v) ? cs_ident<T, OP>() : v);
+      run = cs_scomb<T, OP>(
+          run, cs_lift<T, OP>((v != v) ? cs_ident<T, OP>() : v));
     }
     loc[j] = run;  // inclusive within the thread's segment
   }
   // exclusive base across threads: scan thread totals, read neighbor
-  __shared__ T buf[BLOCK];
+  __shared__ S buf[BLOCK];
   buf[threadIdx.x] = run;
   __syncthreads();
   for (int off = 1; off < BLOCK; off <<= 1) {
-    T add = (threadIdx.x >= off) ? buf[threadIdx.x - off]
-                                 : cs_ident<T, OP>();
+    S add = (threadIdx.x >= off) ? buf[threadIdx.x - off]
+                                 : cs_sident<T, OP>();
     __syncthreads();
-    buf[threadIdx.x] = cs_comb<T, OP>(buf[threadIdx.x], add);
+    buf[threadIdx.x] = cs_scomb<T, OP>(buf[threadIdx.x], add);
     __syncthreads();
   }
-  const T incl = buf[threadIdx.x];
+  const S incl = buf[threadIdx.x];
   __syncthreads();
   buf[threadIdx.x] = incl;
   __syncthreads();
-  const T texcl = (threadIdx.x == 0) ? cs_ident<T, OP>()
+  const S texcl = (threadIdx.x == 0) ? cs_sident<T, OP>()
                                      : buf[threadIdx.x - 1];
-  const T tbase = cs_comb<T, OP>(tile_base[blockIdx.x], texcl);
+  const S tbase = cs_scomb<T, OP>(tile_base[blockIdx.x], texcl);
   __syncthreads();
   for (int j = 0; j < PER; ++j) {
     if (s0 + j < lim) {
       const T v0 = stage[s0 + j];
-      stage[s0 + j] = (v0 != v0) ? v0 : cs_comb<T, OP>(tbase, loc[j]);
+      stage[s0 + j] =
+          (v0 != v0) ? v0 : cs_value<T, OP>(cs_scomb<T, OP>(tbase, loc[j]));
     }
   }
   __syncthreads();
@@ -2701,7 +2758,9 @@ __global__ void __launch_bounds__(BLOCK) k_scatter(
 template <typename T, int OP>
 __global__ void __launch_bounds__(BLOCK) k_seg_tiles(
     const T* __restrict__ in, const int64_t* __restrict__ heads, int64_t n,
-    T* __restrict__ tile_v, unsigned* __restrict__ tile_f) {
+    typename cs_state<T, OP>::type* __restrict__ tile_v,
+    unsigned* __restrict__ tile_f) {
+  using S = typename cs_state<T, OP>::type;
   const int64_t t0 = (int64_t)blockIdx.x * FILT_TILE;
   const int64_t t1 = min(t0 + (int64_t)FILT_TILE, n);
   constexpr int PER = FILT_TILE / BLOCK;
@@ -2718,29 +2777,29 @@ __global__ void __launch_bounds__(BLOCK) k_seg_tiles(
   const int s0 = threadIdx.x * PER;
   const int lim = (int)(t1 - t0);
   unsigned char f = 0;
-  T v = cs_ident<T, OP>();
+  S v = cs_sident<T, OP>();
   for (int j = 0; j < PER; ++j) {
     if (s0 + j < lim) {
       const T x = sv[s0 + j];
-      const T xv = (x != x) ? cs_ident<T, OP>() : x;
+      const S xv = cs_lift<T, OP>((x != x) ? cs_ident<T, OP>() : x);
       if (sf[s0 + j]) { f = 1; v = xv; }
-      else v = cs_comb<T, OP>(v, xv);
+      else v = cs_scomb<T, OP>(v, xv);
     }
   }
-  __shared__ T bv[BLOCK];
+  __shared__ S bv[BLOCK];
   __shared__ unsigned char bf[BLOCK];
   bv[threadIdx.x] = v;
   bf[threadIdx.x] = f;
   __syncthreads();
   for (int off = 1; off < BLOCK; off <<= 1) {
-    T pv = cs_ident<T, OP>();
+    S pv = cs_sident<T, OP>();
     unsigned char pf = 0;
     if (threadIdx.x >= off) { pv = bv[threadIdx.x - off];
                               pf = bf[threadIdx.x - off]; }
     __syncthreads();
     const unsigned char nf = pf | bf[threadIdx.x];
-    const T nv = bf[threadIdx.x] ? bv[threadIdx.x]
-                                 : cs_comb<T, OP>(pv, bv[threadIdx.x]);
+    const S nv = bf[threadIdx.x] ? bv[threadIdx.x]
+                                 : cs_scomb<T, OP>(pv, bv[threadIdx.x]);
     __syncthreads();
     bv[threadIdx.x] = nv;
     bf[threadIdx.x] = nf;
@@ -2754,47 +2813,49 @@ __global__ void __launch_bounds__(BLOCK) k_seg_tiles(
 
 template <typename T, int OP>
 __global__ void __launch_bounds__(1024) k_seg_scan_tiles(
-    T* __restrict__ tile_v, unsigned* __restrict__ tile_f, int64_t ntiles) {
-  __shared__ T carry_v;
+    typename cs_state<T, OP>::type* __restrict__ tile_v,
+    unsigned* __restrict__ tile_f, int64_t ntiles) {
+  using S = typename cs_state<T, OP>::type;
+  __shared__ S carry_v;
   __shared__ unsigned carry_f;
-  if (threadIdx.x == 0) { carry_v = cs_ident<T, OP>(); carry_f = 0; }
-  __shared__ T bv[1024];
+  if (threadIdx.x == 0) { carry_v = cs_sident<T, OP>(); carry_f = 0; }
+  __shared__ S bv[1024];
   __shared__ unsigned char bf[1024];
   __syncthreads();
   for (int64_t base = 0; base < ntiles; base += 1024) {
     const int64_t i = base + threadIdx.x;
-    T v = cs_ident<T, OP>();
+    S v = cs_sident<T, OP>();
     unsigned char f = 0;
     if (i < ntiles) { v = tile_v[i]; f = (unsigned char)tile_f[i]; }
     bv[threadIdx.x] = v;
     bf[threadIdx.x] = f;
     __syncthreads();
     for (int off = 1; off < 1024; off <<= 1) {
-      T pv = cs_ident<T, OP>();
+      S pv = cs_sident<T, OP>();
       unsigned char pf = 0;
       if (threadIdx.x >= off) { pv = bv[threadIdx.x - off];
                                 pf = bf[threadIdx.x - off]; }
       __syncthreads();
       const unsigned char nf = pf | bf[threadIdx.x];
-      const T nv = bf[threadIdx.x] ? bv[threadIdx.x]
-                                   : cs_comb<T, OP>(pv, bv[threadIdx.x]);
+      const S nv = bf[threadIdx.x] ? bv[threadIdx.x]
+                                   : cs_scomb<T, OP>(pv, bv[threadIdx.x]);
       __syncthreads();
       bv[threadIdx.x] = nv;
       bf[threadIdx.x] = nf;
       __syncthreads();
     }
-    const T incl_v = bv[threadIdx.x];
+    const S incl_v = bv[threadIdx.x];
     const unsigned char incl_f = bf[threadIdx.x];
     // exclusive = carry ⊕ previous lane's inclusive (identity at lane 0)
-    const T pv = (threadIdx.x == 0) ? cs_ident<T, OP>()
+    const S pv = (threadIdx.x == 0) ? cs_sident<T, OP>()
                                     : bv[threadIdx.x - 1];
     const unsigned char pf = (threadIdx.x == 0) ? 0 : bf[threadIdx.x - 1];
     const unsigned ef = carry_f | pf;
-    const T ev = pf ? pv : cs_comb<T, OP>(carry_v, pv);
+    const S ev = pf ? pv : cs_scomb<T, OP>(carry_v, pv);
     if (i < ntiles) { tile_v[i] = ev; tile_f[i] = ef; }
     __syncthreads();  // all lanes read carry before 1023 advances it
     if (threadIdx.x == 1023) {
-      carry_v = incl_f ? incl_v : cs_comb<T, OP>(carry_v, incl_v);
+      carry_v = incl_f ? incl_v : cs_scomb<T, OP>(carry_v, incl_v);
       carry_f = carry_f | incl_f;
     }
     __syncthreads();
@@ -2804,8 +2865,9 @@ __global__ void __launch_bounds__(1024) k_seg_scan_tiles(
 template <typename T, int OP>
 __global__ void __launch_bounds__(BLOCK) k_seg_apply(
     const T* __restrict__ in, const int64_t* __restrict__ heads, int64_t n,
-    const T* __restrict__ tile_v, const unsigned* __restrict__ tile_f,
-    T* __restrict__ out) {
+    const typename cs_state<T, OP>::type* __restrict__ tile_v,
+    const unsigned* __restrict__ tile_f, T* __restrict__ out) {
+  using S = typename cs_state<T, OP>::type;
   const int64_t t0 = (int64_t)blockIdx.x * FILT_TILE;
   const int64_t t1 = min(t0 + (int64_t)FILT_TILE, n);
   constexpr int PER = FILT_TILE / BLOCK;
@@ -2821,49 +2883,49 @@ __global__ void __launch_bounds__(BLOCK) k_seg_apply(
   __syncthreads();
   const int s0 = threadIdx.x * PER;
   const int lim = (int)(t1 - t0);
-  T lv[PER];
+  S lv[PER];
   unsigned char lf[PER];
   unsigned char f = 0;
-  T v = cs_ident<T, OP>();
+  S v = cs_sident<T, OP>();
   for (int j = 0; j < PER; ++j) {
     if (s0 + j < lim) {
       const T x = sv[s0 + j];
-      const T xv = (x != x) ? cs_ident<T, OP>() : x;
+      const S xv = cs_lift<T, OP>((x != x) ? cs_ident<T, OP>() : x);
       if (sf[s0 + j]) { f = 1; v = xv; }
-      else v = cs_comb<T, OP>(v, xv);
+      else v = cs_scomb<T, OP>(v, xv);
     }
     lv[j] = v;  // inclusive pair within the thread's run, per element
     lf[j] = f;
   }
-  __shared__ T bv[BLOCK];
+  __shared__ S bv[BLOCK];
   __shared__ unsigned char bf[BLOCK];
   bv[threadIdx.x] = v;
   bf[threadIdx.x] = f;
   __syncthreads();
   for (int off = 1; off < BLOCK; off <<= 1) {
-    T pv = cs_ident<T, OP>();
+    S pv = cs_sident<T, OP>();
     unsigned char pf = 0;
     if (threadIdx.x >= off) { pv = bv[threadIdx.x - off];
                               pf = bf[threadIdx.x - off]; }
     __syncthreads();
     const unsigned char nf = pf | bf[threadIdx.x];
-    const T nv = bf[threadIdx.x] ? bv[threadIdx.x]
-                                 : cs_comb<T, OP>(pv, bv[threadIdx.x]);
+    const S nv = bf[threadIdx.x] ? bv[threadIdx.x]
+                                 : cs_scomb<T, OP>(pv, bv[threadIdx.x]);
     __syncthreads();
     bv[threadIdx.x] = nv;
     bf[threadIdx.x] = nf;
     __syncthreads();
   }
   // thread base = tile exclusive pair ⊕ preceding threads' inclusive pair
-  const T pv = (threadIdx.x == 0) ? cs_ident<T, OP>() : bv[threadIdx.x - 1];
+  const S pv = (threadIdx.x == 0) ? cs_sident<T, OP>() : bv[threadIdx.x - 1];
   const unsigned char pf = (threadIdx.x == 0) ? 0 : bf[threadIdx.x - 1];
-  const T base_v = pf ? pv : cs_comb<T, OP>(tile_v[blockIdx.x], pv);
+  const S base_v = pf ? pv : cs_scomb<T, OP>(tile_v[blockIdx.x], pv);
   __syncthreads();
   for (int j = 0; j < PER; ++j) {
     if (s0 + j < lim) {
       const T x = sv[s0 + j];
-      const T r = lf[j] ? lv[j] : cs_comb<T, OP>(base_v, lv[j]);
-      sv[s0 + j] = (x != x) ? x : r;
+      const S r = lf[j] ? lv[j] : cs_scomb<T, OP>(base_v, lv[j]);
+      sv[s0 + j] = (x != x) ? x : cs_value<T, OP>(r);
     }
   }
   __syncthreads();
@@ -4439,27 +4501,28 @@ int hf_cumsum(const hf_col* col, int agg_op, hf_col** out) {
   if (rc != HF_OK) return rc;
   if (n == 0) { o.commit(out); return HF_OK; }
   const int64_t ntiles = (n + FILT_TILE - 1) / FILT_TILE;
-  DevBuf ts;
-  HF_HIP("hf_cumsum", ts.alloc(ntiles * 8));
+  DevBuf ts;  // per-tile scan state; 16 B holds the f64 product's pair
+  HF_HIP("hf_cumsum", ts.alloc(ntiles * sizeof(cs_dd)));
   rc = with_scan_op(agg_op, [&](auto opTag) {
     return with_dtype(col->dtype, [&](auto tTag) -> int {
       using T = decltype(tTag);
       constexpr int OP = decltype(opTag)::value;
+      using S = typename cs_state<T, OP>::type;
       int r2 = timed_launch("cumsum_tiles", [&] {
         hipLaunchKernelGGL((k_cumsum_tiles<T, OP>), dim3((uint32_t)ntiles),
                            dim3(BLOCK), 0, g.stream, (const T*)col->dptr, n,
-                           ts.as<T>());
+                           ts.as<S>());
       });
       if (r2 != HF_OK) return r2;
       r2 = timed_launch("cumsum_scan", [&] {
         hipLaunchKernelGGL((k_cumsum_scan_tiles<T, OP>), dim3(1), dim3(1024),
-                           0, g.stream, ts.as<T>(), ntiles);
+                           0, g.stream, ts.as<S>(), ntiles);
       });
       if (r2 != HF_OK) return r2;
       return timed_launch("cumsum_apply", [&] {
         hipLaunchKernelGGL((k_cumsum_apply<T, OP>), dim3((uint32_t)ntiles),
                            dim3(BLOCK), 0, g.stream, (const T*)col->dptr, n,
-                           (const T*)ts.as<T>(), o.data<T>());
+                           (const S*)ts.as<S>(), o.data<T>());
       });
     });
   });
@@ -4484,29 +4547,30 @@ int hf_seg_cumsum(const hf_col* col, const hf_col* heads, int agg_op,
   if (n == 0) { o.commit(out); return HF_OK; }
   const int64_t ntiles = (n + FILT_TILE - 1) / FILT_TILE;
   DevBuf tv, tf;
-  HF_HIP("hf_seg_cumsum", tv.alloc(ntiles * 8));
+  HF_HIP("hf_seg_cumsum", tv.alloc(ntiles * sizeof(cs_dd)));
   HF_HIP("hf_seg_cumsum", tf.alloc(ntiles * 4));
   rc = with_scan_op(agg_op, [&](auto opTag) {
     return with_dtype(col->dtype, [&](auto tTag) -> int {
       using T = decltype(tTag);
       constexpr int OP = decltype(opTag)::value;
+      using S = typename cs_state<T, OP>::type;
       int r2 = timed_launch("seg_tiles", [&] {
         hipLaunchKernelGGL((k_seg_tiles<T, OP>), dim3((uint32_t)ntiles),
                            dim3(BLOCK), 0, g.stream, (const T*)col->dptr,
-                           (const int64_t*)heads->dptr, n, tv.as<T>(),
+                           (const int64_t*)heads->dptr, n, tv.as<S>(),
                            tf.as<unsigned>());
       });
       if (r2 != HF_OK) return r2;
       r2 = timed_launch("seg_scan", [&] {
         hipLaunchKernelGGL((k_seg_scan_tiles<T, OP>), dim3(1), dim3(1024),
-                           0, g.stream, tv.as<T>(), tf.as<unsigned>(), ntiles);
+                           0, g.stream, tv.as<S>(), tf.as<unsigned>(), ntiles);
       });
       if (r2 != HF_OK) return r2;
       return timed_launch("seg_apply", [&] {
         hipLaunchKernelGGL((k_seg_apply<T, OP>), dim3((uint32_t)ntiles),
                            dim3(BLOCK), 0, g.stream, (const T*)col->dptr,
                            (const int64_t*)heads->dptr, n,
-                           (const T*)tv.as<T>(),
+                           (const S*)tv.as<S>(),
                            (const unsigned*)tf.as<unsigned>(), o.data<T>());
       });
     });
