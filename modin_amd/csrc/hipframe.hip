@@ -882,6 +882,12 @@ constexpr int GB_RANGE = 1 << GB_RANGE_LOG;
 constexpr int64_t GB_MAX_BUCKETS = 1024;       // radix path: n_slots <= 4.2M
 constexpr int64_t GB_DENSE_MAX = 8192;         // direct-LDS path bound
 constexpr int64_t AGG_CHUNK = 1 << 21;         // rows per P2 work item
+// Row pairs a lane has in flight in the two streaming aggregates, chosen by
+// A/B from {2, 4, 8} (profiles/r08): P2 runs 1.71 -> 1.61 ms at 2 and within
+// 0.02 ms of the one-pair loop at 4 and 8; k_gb_dense 4.29 -> 3.03 / 2.87 /
+// 2.87 ms at 2 / 4 / 8 (8 costs 117 VGPRs for nothing measurable).
+constexpr int GB_P2_U = 2;                     // k_gb_bucket_agg
+constexpr int GB_DENSE_U = 4;                  // k_gb_dense
 
 struct GbWorkItem {
   int64_t start;   // absolute row in the scatter regions
@@ -1316,16 +1322,54 @@ __global__ void __launch_bounds__(512) k_gb_bucket_agg(
       }
     }
   };
-  for (int64_t i = threadIdx.x; i < npair; i += blockDim.x) {
-    const ushort2 kk = k2[i];
+  // both streams are read once: non-temporal loads (the builtin takes native
+  // scalars and vectors, hence the u32 / ext_vector views of a pair);
+  // P2 1.70 -> 1.56 ms on top of the two-pair loop (profiles/r08)
+  auto ld_k = [&](int64_t i) {
+    const unsigned r = __builtin_nontemporal_load(
+        reinterpret_cast<const unsigned*>(k2) + i);
+    return make_ushort2((unsigned short)(r & 0xFFFFu),
+                        (unsigned short)(r >> 16));
+  };
+  auto ld_v = [&](int64_t i) {
+    typedef double nd2 __attribute__((ext_vector_type(2)));
+    const nd2 r = __builtin_nontemporal_load(
+        reinterpret_cast<const nd2*>(v2) + i);
+    return make_double2(r.x, r.y);
+  };
+  auto feed_pair = [&](ushort2 kk, double2 vv) {
     if (HAVE_VAL) {
-      const double2 vv = v2[i];
       feed(kk.x, vv.x);
       feed(kk.y, vv.y);
     } else {
       ltouch[kk.x] = 1;
       ltouch[kk.y] = 1;
     }
+  };
+  // GB_P2_U pairs in flight per lane: a body trip issues the loads of U
+  // block-strides, then feeds them in stride order, so a lane sees the rows
+  // it would see one stride at a time, in that order.  The trip condition is
+  // block-uniform; the last < U * blockDim.x pairs go one stride at a time.
+  constexpr int U = GB_P2_U;
+  const int64_t bstep = (int64_t)U * blockDim.x;
+  int64_t base = 0;
+  for (; base + bstep <= npair; base += bstep) {
+    ushort2 kk[U];
+    double2 vv[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = base + (int64_t)u * blockDim.x + threadIdx.x;
+      kk[u] = ld_k(i);
+      if (HAVE_VAL) vv[u] = ld_v(i);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) feed_pair(kk[u], vv[u]);
+  }
+  for (int64_t i = base + threadIdx.x; i < npair; i += blockDim.x) {
+    const ushort2 kk = ld_k(i);
+    double2 vv = make_double2(0.0, 0.0);
+    if (HAVE_VAL) vv = ld_v(i);
+    feed_pair(kk, vv);
   }
   flush();
   if (((end - a0) & 1) && threadIdx.x == 0) one_row(end - 1);
@@ -1422,23 +1466,55 @@ __global__ void __launch_bounds__(512) k_gb_dense(
     if (CNT) lcnt[s] = 0;
   }
   __syncthreads();
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) {
-    const int64_t k = keys[i] - key_min;
+  auto row = [&](int64_t key, double v) {
+    const int64_t k = key - key_min;
     if ((uint64_t)k >= (uint64_t)n_slots) {
       atomicAdd(err, 1ULL);
-      continue;
+      return;
     }
     ltouch[k] = 1;  // presence-only (plain LDS byte store, CU-local)
-    if (HAVE_VAL) {
-      const double v = vals[i];
-      if (v == v) {
-        lds_slot_agg<AOP>(&lsums[k], v);
-        if (CNT) atomicAdd(&lcnt[k], 1u);
-      }
+    if (HAVE_VAL && v == v) {
+      lds_slot_agg<AOP>(&lsums[k], v);
+      if (CNT) atomicAdd(&lcnt[k], 1u);
+    }
+  };
+  // 2 rows/lane vectorized, block-strided over row pairs.  INVARIANT: keys
+  // and vals are column buffers straight from the device allocator (hipMalloc
+  // blocks, 256-byte aligned; a column never points into another's block), so
+  // the longlong2/double2 casts are 16-byte aligned from row 0.
+  const longlong2* k2 = reinterpret_cast<const longlong2*>(keys);
+  const double2* v2 = reinterpret_cast<const double2*>(vals);
+  const int64_t npair = n >> 1;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  // GB_DENSE_U pairs in flight per lane: a body trip issues the loads of U
+  // grid-strides before it consumes the first; the trip condition is
+  // block-uniform, the rest goes one stride at a time.
+  constexpr int U = GB_DENSE_U;
+  int64_t p0 = (int64_t)blockIdx.x * blockDim.x;
+  for (; p0 + (U - 1) * stride + blockDim.x <= npair; p0 += U * stride) {
+    longlong2 kk[U];
+    double2 vv[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t p = p0 + u * stride + threadIdx.x;
+      kk[u] = k2[p];
+      if (HAVE_VAL) vv[u] = v2[p];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      row(kk[u].x, HAVE_VAL ? vv[u].x : 0.0);
+      row(kk[u].y, HAVE_VAL ? vv[u].y : 0.0);
     }
   }
+  for (int64_t p = p0 + threadIdx.x; p < npair; p += stride) {
+    const longlong2 kk = k2[p];
+    double2 vv = make_double2(0.0, 0.0);
+    if (HAVE_VAL) vv = v2[p];
+    row(kk.x, vv.x);
+    row(kk.y, vv.y);
+  }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0)
+    row(keys[n - 1], HAVE_VAL ? vals[n - 1] : 0.0);
   __syncthreads();
   for (int64_t s = threadIdx.x; s < n_slots; s += blockDim.x) {
     if (!ltouch[s]) continue;
