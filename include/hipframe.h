@@ -280,6 +280,12 @@ int hf_groupby_reduce(const hf_col* keys, const hf_col* const* vals,
                       hf_col** out_keys, hf_col** out_sums,
                       hf_col** out_counts, int64_t* n_groups);
 
+/* Bucket width (log2) the radix path uses for a key range of n_slots, with or
+ * without per-column counts: 12, 13 or 14, or 0 where the range is too wide
+ * for the radix path.  Pure: needs no hf_init and touches no device.  Ranges
+ * of at most 8192 slots take the dense path whatever this returns. */
+int hf_groupby_radix_rl(int64_t n_slots, int want_counts);
+
 /* ---- Join: broadcast-right hash (dense-range CSR) inner join ----
  * Device form of MergeImpl.row_axis_merge
  * (modin/core/storage_formats/pandas/merge.py:104-178: materialize the right

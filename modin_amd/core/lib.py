@@ -176,6 +176,7 @@ def load() -> ct.CDLL:
                                              ct.POINTER(ct.c_void_p),
                                              ct.POINTER(ct.c_void_p),
                                              ct.POINTER(ct.c_int64)]),
+            "hf_groupby_radix_rl": (ct.c_int, [ct.c_int64, ct.c_int]),
             "hf_col_concat": (ct.c_int, [ct.POINTER(ct.c_void_p), ct.c_int,
                                          ct.POINTER(ct.c_void_p)]),
             "hf_col_slice": (ct.c_int, [ct.c_void_p, ct.c_int64, ct.c_int64,
@@ -223,7 +224,8 @@ def exported_symbols():
         "hf_memset_raw", "hf_dev_live", "hf_map_scalar", "hf_map_scalar_i64",
         "hf_binary",
         "hf_reduce", "hf_groupby_accum", "hf_group_moments",
-        "hf_groupby_compact", "hf_groupby_reduce", "hf_fill_f64",
+        "hf_groupby_compact", "hf_groupby_reduce", "hf_groupby_radix_rl",
+        "hf_fill_f64",
         "hf_fixup_empty", "hf_sort_perm", "hf_fill_i64",
         "hf_fill_randint", "hf_fill_randf64", "hf_fill_randcdf",
         "hf_groupby_hash_accum", "hf_groupby_hash_compact",
@@ -621,6 +623,13 @@ def groupby_reduce(keys: ColumnRef, vals: list, agg_op: int,
     ccols = ([_wrap(ct.c_void_p(out_counts[c]), n, HF_INT64)
               for c in range(nvals)] if want_counts else None)
     return kcol, scols, ccols, n
+
+
+def groupby_radix_rl(n_slots: int, want_counts: bool) -> int:
+    """Bucket width (log2) the radix groupby uses for a key range of n_slots:
+    12, 13 or 14, or 0 where the range is too wide (hf_groupby_radix_rl).
+    Pure: needs no GPU."""
+    return load().hf_groupby_radix_rl(n_slots, 1 if want_counts else 0)
 
 
 def col_slice(col: ColumnRef, start: int, length: int) -> ColumnRef:

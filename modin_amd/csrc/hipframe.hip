@@ -229,6 +229,12 @@ int with_nvals(int nv, F&& f) {  // nv in [0, MAX]
   else
     return set_err(HF_ERR_ARG, "with_nvals", "column count out of range");
 }
+// Radix bucket width (log2): what gb_radix_rl returns when it is not 0.
+template <typename F>
+int with_rl(int rl, F&& f) {
+  return rl == 14 ? f(int_tag<14>{})
+         : rl == 13 ? f(int_tag<13>{}) : f(int_tag<12>{});
+}
 // The scan ops are with_aop's plus PROD.  Kept apart from with_aop, whose
 // groupby callers would otherwise instantiate PROD kernels they never launch.
 template <typename F>
@@ -1254,9 +1260,14 @@ __global__ void k_gb_plan_err(const unsigned long long* __restrict__ meta,
 // stores its whole table — identity in untouched slots — as row blockIdx.x of
 // part_sums / part_cnt with plain 16-byte stores; k_gb_combine folds the rows
 // of a bucket.
+// A 16384-slot table (RL = 14, sums without counts) is 128 KB, so one block
+// fits a CU: it runs 1024 threads, the same 16 waves per CU as two 512-thread
+// blocks at RL = 13.  The loops stride by blockDim.x.
+constexpr int gb_p2_block(int rl) { return rl >= 14 ? 1024 : 512; }
+
 template <bool ROWCNT, bool CNT, bool HAVE_VAL, int RL, int AOP,
           bool PART = false>
-__global__ void __launch_bounds__(512) k_gb_bucket_agg(
+__global__ void __launch_bounds__(gb_p2_block(RL)) k_gb_bucket_agg(
     const double* __restrict__ vals, const unsigned short* __restrict__ lowkeys,
     const GbWorkItem* __restrict__ work, int64_t n_slots,
     double* __restrict__ gsums, unsigned long long* __restrict__ growcnt,
@@ -1264,6 +1275,8 @@ __global__ void __launch_bounds__(512) k_gb_bucket_agg(
     double* __restrict__ part_sums = nullptr,   // [gridDim.x][RANGE] (PART)
     unsigned* __restrict__ part_cnt = nullptr) {  // likewise, with CNT
   static_assert(!PART || (HAVE_VAL && !ROWCNT), "PART flushes value tables");
+  static_assert(RL <= 16, "low keys are u16");
+  static_assert(RL <= 13 || !CNT, "no LDS for a counts table beside 16384 sums");
   constexpr int RANGE = 1 << RL;
   __shared__ __attribute__((aligned(16))) double lsums[HAVE_VAL ? RANGE : 1];
   __shared__ __attribute__((aligned(16))) unsigned lcnt[CNT ? RANGE : 1];
@@ -3905,7 +3918,8 @@ int radix_agg(const GbRadixCall& a, const double* v, double* gs,
   const GbKeyCache& kc = a.keys->gb;
   return timed_launch("gb_bucket_agg", [&] {
     hipLaunchKernelGGL((k_gb_bucket_agg<R, C, V, RL, AOP>),
-                       dim3((uint32_t)kc.work_n), dim3(512), 0, g.stream, v,
+                       dim3((uint32_t)kc.work_n), dim3(gb_p2_block(RL)), 0,
+                       g.stream, v,
                        a.rk, (const GbWorkItem*)kc.d_work, a.n_slots, gs,
                        growcnt, gc);
   });
@@ -3915,12 +3929,38 @@ int radix_agg(const GbRadixCall& a, const double* v, double* gs,
 // Sum-only uses 8192-key buckets (bigger scatter chunks; the u8-touch agg
 // table still fits 2 blocks/CU); count/mean use 4096 (3 blocks/CU with the
 // counts table).
+// Sum-only calls on more than GB_RL14_ABOVE slots use 16384-key buckets:
+// half as many buckets make the write runs of a replay tile twice as long
+// (profiles/r09).  Up to that bound 8192-key buckets number at most 32, so a
+// 12288-row tile already writes runs of 384 rows and more, where the measured
+// run-length curve is flat (3.62 ms at 396 rows, 3.65 at 792).  HF_GB_RL=13
+// (read once) keeps 8192-key buckets, for A/B runs inside one build.
+constexpr int64_t GB_RL14_ABOVE = 1 << 18;
 int gb_radix_rl(int64_t n_slots, bool want_cnt) {
+  static const bool rl14_env = [] {
+    const char* e = getenv("HF_GB_RL");
+    return !(e && strcmp(e, "13") == 0);
+  }();
   const int64_t nb13 = (n_slots + (1 << 13) - 1) >> 13;
   const int64_t nb12 = (n_slots + (1 << 12) - 1) >> 12;
-  return (!want_cnt && nb13 <= GB_MAX_BUCKETS) ? 13
-         : (want_cnt && nb12 <= GB_MAX_BUCKETS) ? 12
+  if (!want_cnt && nb13 <= GB_MAX_BUCKETS)
+    return (rl14_env && n_slots > GB_RL14_ABOVE) ? 14 : 13;
+  return (want_cnt && nb12 <= GB_MAX_BUCKETS) ? 12
          : (nb13 <= GB_MAX_BUCKETS) ? 13 : 0;
+}
+
+// with_bool on want-counts.  RL = 14 has no counts instantiation (its LDS
+// would not fit) and gb_radix_rl never selects it with counts.
+template <int RL, typename F>
+int with_cnt(bool cnt, F&& f) {
+  if constexpr (RL >= 14) {
+    if (cnt)
+      return set_err(HF_ERR_UNSUPPORTED, "gb_radix",
+                     "16384-slot buckets carry no counts");
+    return f(std::false_type{});
+  } else {
+    return with_bool(cnt, std::forward<F>(f));
+  }
 }
 
 // The steady state of hf_groupby_reduce on a column whose plan is recorded
@@ -3958,13 +3998,14 @@ int gb_radix_mapped(hf_col* keys, const GbPtrs& ptrs, int nvals,
     if (rc == HF_OK && want_counts) rc = o.cnts[c].alloc(ng, HF_INT64);
     if (rc == HF_OK) rc = radix_replay(a, ptrs.vals[c], false);
     if (rc != HF_OK) return rc;
-    rc = with_bool(want_counts, [&](auto cTag) {
+    rc = with_cnt<RL>(want_counts, [&](auto cTag) {
       constexpr bool C = decltype(cTag)::value;
       int r = timed_launch("gb_bucket_agg", [&] {
         hipLaunchKernelGGL(
             (k_gb_bucket_agg<false, C, true, RL, AOP, true>),
-            dim3((uint32_t)kc.work_n), dim3(512), 0, g.stream, a.r0, a.rk,
-            (const GbWorkItem*)kc.d_work, n_slots, nullptr, nullptr, nullptr,
+            dim3((uint32_t)kc.work_n), dim3(gb_p2_block(RL)), 0, g.stream,
+            a.r0, a.rk, (const GbWorkItem*)kc.d_work, n_slots, nullptr,
+            nullptr, nullptr,
             part_sums.as<double>(), part_cnt.as<unsigned>());
       });
       if (r != HF_OK) return r;
@@ -4046,7 +4087,7 @@ int gb_radix_path(hf_col* keys, const GbPtrs& ptrs, int nvals, int64_t key_min,
     unsigned long long* gc =
         cnt ? (unsigned long long*)counts + (int64_t)c * n_slots : nullptr;
     rc = with_bool(c == 0 && with_rowcnt, [&](auto rTag) {
-      return with_bool(cnt, [&](auto cTag) {
+      return with_cnt<RL>(cnt, [&](auto cTag) {
         return radix_agg<RL, AOP, decltype(rTag)::value,
                          decltype(cTag)::value, true>(a, v, gs, growcnt, gc);
       });
@@ -4101,11 +4142,11 @@ int hf_groupby_accum(const hf_col* keys, const hf_col* const* vals, int nvals,
         const uintptr_t csub =
             counts ? counts + (uintptr_t)c0 * n_slots * 8 : 0;
         auto radix = [&](auto rlTag) {
-          return gb_radix_path<decltype(rlTag)::value ? 13 : 12, AOP>(
+          return gb_radix_path<decltype(rlTag)::value, AOP>(
               const_cast<hf_col*>(keys), sub, nv, key_min, n_slots, ssub,
               rowcnt, csub, d_err, c0 == 0);
         };
-        rc2 = with_bool(rl_ok == 13, radix);
+        rc2 = with_rl(rl_ok, radix);
         if (nvals == 0) break;
       }
       return rc2;
@@ -4297,6 +4338,10 @@ int hf_groupby_compact(uintptr_t sums, uintptr_t rowcnt, uintptr_t counts,
                     out_sums, out_counts, n_groups, nullptr);
 }
 
+int hf_groupby_radix_rl(int64_t n_slots, int want_counts) {
+  return n_slots > 0 ? gb_radix_rl(n_slots, want_counts != 0) : 0;
+}
+
 int hf_groupby_reduce(const hf_col* keys, const hf_col* const* vals, int nvals,
                       int agg_op, int want_counts, int64_t key_min,
                       int64_t n_slots, hf_col** out_keys, hf_col** out_sums,
@@ -4329,8 +4374,8 @@ int hf_groupby_reduce(const hf_col* keys, const hf_col* const* vals, int nvals,
   if (plan_ok && kc.d_gidx) {
     GroupOut o(nvals, cnt);
     const int rc = with_aop(agg_op, [&](auto aopTag) {
-      return with_bool(rl == 13, [&](auto rlTag) {
-        return gb_radix_mapped<decltype(rlTag)::value ? 13 : 12,
+      return with_rl(rl, [&](auto rlTag) {
+        return gb_radix_mapped<decltype(rlTag)::value,
                                decltype(aopTag)::value>(
             kcol, ptrs, nvals, key_min, n_slots, cnt, o);
       });
