@@ -342,6 +342,13 @@ enum {
 int hf_compare_scalar(int op, const hf_col* col, double scalar,
                       hf_col** out);  /* int64 0/1 mask; NaN compares false
                                          except NE (pandas semantics) */
+/* int64 column against an exact int64 scalar.  hf_compare_scalar promotes an
+ * int64 row to double, which is what pandas does against a float operand but
+ * merges neighbours above 2^53 (datetime64[ns] values sit near 1.7e18, where
+ * one double ulp is 256 ns); an integer or Timestamp operand takes this entry.
+ * HF_ERR_ARG for a non-int64 column; HF_CMP_NOTNA is all ones. */
+int hf_compare_scalar_i64(int op, const hf_col* col, int64_t scalar,
+                          hf_col** out);
 
 typedef struct hf_filterplan hf_filterplan;
 int hf_filter_plan(const hf_col* mask, hf_filterplan** out, int64_t* n_kept);

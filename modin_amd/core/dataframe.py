@@ -2449,7 +2449,7 @@ class HipDataframe:
             elif c.dtype_code == lib.HF_FLOAT64:
                 m = lib.compare_scalar(lib.CMP_NOTNA, c, 0.0)
             elif b in dtc:
-                m = lib.compare_scalar(lib.CMP_NE, c, float(INAT))
+                m = lib.compare_scalar(lib.CMP_NE, c, INAT)
             else:
                 continue
             valid = m if valid is None else lib.binary(lib.BIN_MUL, valid, m)
@@ -2580,7 +2580,7 @@ class HipDataframe:
         if n and lib.reduce(ns).imn == INAT:
             # NaT rows -> NaN, float64 result (the pandas dtype rule when
             # NaT is present)
-            notnat = lib.compare_scalar(lib.CMP_NE, ns, float(INAT))
+            notnat = lib.compare_scalar(lib.CMP_NE, ns, INAT)
             out = lib.fixup_empty(lib.cast_f64(out), notnat)
             part = HipDataframePartition(DeviceBlock({name: out}, n))
             return HipDataframe([part], self._index, [name], [n],
@@ -3939,13 +3939,16 @@ class HipDataframe:
                         raise lib.HfError(
                             f"comparing numeric column {name!r} to a "
                             "string scalar")
-                    m = lib.compare_scalar(op_code, col, float(scalar))
+                    # integers (Timestamp ns among them) stay integers: an
+                    # int64 column compares with them exactly, not via f64
+                    s = scalar if isinstance(scalar, (int, np.integer)) \
+                        else float(scalar)
+                    m = lib.compare_scalar(op_code, col, s)
                     if name in dtc:
                         # pandas NaT semantics: every ordered compare is
                         # False on NaT rows (NE stays True — IEEE-NaN
                         # style); NOTNA is exactly (!= iNaT)
-                        notnat = lib.compare_scalar(lib.CMP_NE, col,
-                                                    float(INAT))
+                        notnat = lib.compare_scalar(lib.CMP_NE, col, INAT)
                         if op_code == lib.CMP_NOTNA:
                             m = notnat
                         elif op_code != lib.CMP_NE:
@@ -4234,7 +4237,7 @@ class HipDataframe:
             # NaT rows jump above (na last) / below (na first) every
             # valid ns value, valid keys keep or negate their order
             NANKEY = ((1 << 63) - 1) * (-1 if na_first else 1)
-            notnat = lib.compare_scalar(lib.CMP_NE, col, float(INAT))
+            notnat = lib.compare_scalar(lib.CMP_NE, col, INAT)
             nat_big = lib.map_scalar(
                 lib.MAP_MUL, lib.map_scalar(lib.MAP_RSUB, notnat, 1),
                 NANKEY)
@@ -4390,7 +4393,7 @@ class HipDataframe:
                 if name in block.cats:  # dict-encoded: NaN is code −1
                     m = lib.compare_scalar(lib.CMP_NE, col, -1.0)
                 elif name in dtc:  # datetime: NaT is iNaT
-                    m = lib.compare_scalar(lib.CMP_NE, col, float(INAT))
+                    m = lib.compare_scalar(lib.CMP_NE, col, INAT)
                 else:
                     m = lib.compare_scalar(lib.CMP_NOTNA, col, 0.0)
                 acc = m if acc is None else lib.binary(lib.BIN_MUL, acc, m)

@@ -195,6 +195,9 @@ def load() -> ct.CDLL:
             "hf_compare_scalar": (ct.c_int, [ct.c_int, ct.c_void_p,
                                              ct.c_double,
                                              ct.POINTER(ct.c_void_p)]),
+            "hf_compare_scalar_i64": (ct.c_int, [ct.c_int, ct.c_void_p,
+                                                 ct.c_int64,
+                                                 ct.POINTER(ct.c_void_p)]),
             "hf_filter_plan": (ct.c_int, [ct.c_void_p, ct.POINTER(ct.c_void_p),
                                           ct.POINTER(ct.c_int64)]),
             "hf_filter_apply": (ct.c_int, [ct.c_void_p, ct.c_void_p,
@@ -233,7 +236,8 @@ def exported_symbols():
         "hf_search_sorted", "hf_ordered_i64", "hf_cumsum", "hf_seg_cumsum",
         "hf_ewm_mean", "hf_scatter", "hf_cross_idx",
         "hf_col_concat", "hf_col_slice", "hf_join_build", "hf_join_free", "hf_join_probe",
-        "hf_gather", "hf_compare_scalar", "hf_filter_plan", "hf_filter_apply",
+        "hf_gather", "hf_compare_scalar", "hf_compare_scalar_i64",
+        "hf_filter_plan", "hf_filter_apply",
         "hf_filter_iota", "hf_filter_plan_free", "hf_profiling",
         "hf_kernel_stats", "hf_kernel_stats_reset",
     ]
@@ -696,9 +700,20 @@ def join_probe(j: JoinRef, lkeys: ColumnRef):
 CMP_GT, CMP_GE, CMP_LT, CMP_LE, CMP_EQ, CMP_NE, CMP_NOTNA = range(7)
 
 
-def compare_scalar(op: int, col: ColumnRef, scalar: float) -> ColumnRef:
+def compare_scalar(op: int, col: ColumnRef, scalar) -> ColumnRef:
+    """int64 0/1 mask of `col <op> scalar`.  An int64 column against an
+    integer that fits int64 compares exactly; everything else (float scalar,
+    out-of-range int, f64 column) compares in float64, as pandas/numpy
+    promote."""
     ensure_ready()
     out = ct.c_void_p()
+    if (col.dtype_code == HF_INT64
+            and isinstance(scalar, (int, np.integer))
+            and -2**63 <= int(scalar) < 2**63):
+        _check(load().hf_compare_scalar_i64(op, col.handle, int(scalar),
+                                            ct.byref(out)),
+               "hf_compare_scalar_i64")
+        return _wrap(out, col.length, HF_INT64)
     _check(load().hf_compare_scalar(op, col.handle, float(scalar),
                                     ct.byref(out)), "hf_compare_scalar")
     return _wrap(out, col.length, HF_INT64)

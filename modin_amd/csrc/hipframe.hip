@@ -2397,8 +2397,10 @@ __global__ void __launch_bounds__(BLOCK) k_fixup_empty(
 
 // ---- compare + filter kernels ----
 
-template <int OP, typename T>
-__device__ __forceinline__ long long cmp1(T x, double s) {
+// S is the scalar's type: double (an int64 row is promoted to double, as
+// pandas does against a float operand) or long long (exact int64 compare)
+template <int OP, typename T, typename S>
+__device__ __forceinline__ long long cmp1(T x, S s) {
   switch (OP) {
     case HF_CMP_GT: return x > s;
     case HF_CMP_GE: return x >= s;
@@ -2411,13 +2413,13 @@ __device__ __forceinline__ long long cmp1(T x, double s) {
   return 0;
 }
 
-template <int OP, typename T>
+template <int OP, typename T, typename S>
 __global__ void __launch_bounds__(BLOCK) k_compare(const T* __restrict__ in,
                                                    long long* __restrict__ out,
-                                                   double s, int64_t n) {
+                                                   S s, int64_t n) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) out[i] = cmp1<OP, T>(in[i], s);
+  for (; i < n; i += stride) out[i] = cmp1<OP, T, S>(in[i], s);
 }
 
 constexpr int FILT_TILE = 4096;
@@ -5500,7 +5502,7 @@ int hf_compare_scalar(int op, const hf_col* col, double scalar, hf_col** out) {
     constexpr int O = decltype(opTag)::value;
     using T = typename decltype(tTag)::type;
     return timed_launch("compare", [&] {
-      hipLaunchKernelGGL((k_compare<O, T>), dim3((uint32_t)grid_for(n)),
+      hipLaunchKernelGGL((k_compare<O, T, double>), dim3((uint32_t)grid_for(n)),
                          dim3(BLOCK), 0, g.stream, (const T*)col->dptr,
                          o.data<long long>(), scalar, n);
     });
@@ -5511,6 +5513,38 @@ int hf_compare_scalar(int op, const hf_col* col, double scalar, hf_col** out) {
   switch (op) {
 #define HF_CMP_CASE(O) \
   case O: rc = f ? L(int_tag<O>{}, F64{}) : L(int_tag<O>{}, I64{}); break;
+    HF_CMP_CASE(HF_CMP_GT) HF_CMP_CASE(HF_CMP_GE) HF_CMP_CASE(HF_CMP_LT)
+    HF_CMP_CASE(HF_CMP_LE) HF_CMP_CASE(HF_CMP_EQ) HF_CMP_CASE(HF_CMP_NE)
+    HF_CMP_CASE(HF_CMP_NOTNA)
+#undef HF_CMP_CASE
+  }
+  return o.commit_if(rc, out);
+}
+
+int hf_compare_scalar_i64(int op, const hf_col* col, int64_t scalar,
+                          hf_col** out) {
+  HF_NEED_INIT("hf_compare_scalar_i64");
+  if (!col || !out) return set_err(HF_ERR_ARG, "hf_compare_scalar_i64", "null");
+  if (op < HF_CMP_GT || op > HF_CMP_NOTNA)
+    return set_err(HF_ERR_ARG, "hf_compare_scalar_i64", "unknown op");
+  if (col->dtype != HF_INT64)
+    return set_err(HF_ERR_ARG, "hf_compare_scalar_i64", "int64 column required");
+  ColOut o;
+  int rc = o.alloc(col->len, HF_INT64);
+  if (rc != HF_OK) return rc;
+  const int64_t n = col->len;
+  const long long s = (long long)scalar;
+  auto L = [&](auto opTag) {
+    constexpr int O = decltype(opTag)::value;
+    return timed_launch("compare", [&] {
+      hipLaunchKernelGGL((k_compare<O, long long, long long>),
+                         dim3((uint32_t)grid_for(n)), dim3(BLOCK), 0, g.stream,
+                         (const long long*)col->dptr, o.data<long long>(), s, n);
+    });
+  };
+  switch (op) {
+#define HF_CMP_CASE(O) \
+  case O: rc = L(int_tag<O>{}); break;
     HF_CMP_CASE(HF_CMP_GT) HF_CMP_CASE(HF_CMP_GE) HF_CMP_CASE(HF_CMP_LT)
     HF_CMP_CASE(HF_CMP_LE) HF_CMP_CASE(HF_CMP_EQ) HF_CMP_CASE(HF_CMP_NE)
     HF_CMP_CASE(HF_CMP_NOTNA)

@@ -663,7 +663,7 @@ class HipQueryCompiler:
         r = lib.binary(lib.BIN_SUB, ns,
                        lib.map_scalar(lib.MAP_IMOD, ns, int(unit_ns)))
         if n and lib.reduce(ns).imn == INAT:
-            m = lib.compare_scalar(lib.CMP_NE, ns, float(INAT))
+            m = lib.compare_scalar(lib.CMP_NE, ns, INAT)
             inv = lib.map_scalar(lib.MAP_RSUB, m, 1)
             nat = lib.map_scalar(lib.MAP_MUL, inv, INAT)
             r = lib.binary(lib.BIN_ADD,
