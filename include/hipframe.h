@@ -455,6 +455,70 @@ int hf_cross_idx(int64_t nl, int64_t nr, hf_col** lidx, hf_col** ridx);
 int hf_search_sorted(const hf_col* keys, const hf_col* sorted_uniq,
                      hf_col** out);
 
+/* As-of match positions: pandas merge_asof(direction=..., tolerance=...,
+ * allow_exact_matches=..., by=...) reduced to one index per left row.  The
+ * reference sends merge_asof to pandas on the host
+ * (modin/core/storage_formats/base/query_compiler.py:1713); this is the
+ * device form of the match itself.
+ *
+ * The right side is ascending lexicographically by (rby, ron), or by ron
+ * alone without a by column.  Without by, lon is ascending too; with by, lon
+ * may be in any order.  Neither on column holds a NaN.  For a left row
+ * (b, l), over the m right rows in the pair order (rby, ron):
+ *   backward:  p = upper_bound((b, l)) - 1, or lower_bound - 1 when
+ *              !allow_exact; valid iff p >= 0 and rby[p] == b.  Among equal
+ *              right keys this is the LAST one.
+ *   forward:   p = lower_bound((b, l)), or upper_bound when !allow_exact;
+ *              valid iff p < m and rby[p] == b.  Among equal right keys this
+ *              is the FIRST one.
+ *   tolerance: with has_tol, a candidate with |l - ron[p]| > tol is dropped.
+ *              An int64 distance is the UNSIGNED 64-bit difference of the
+ *              ordered pair, compared with (uint64_t)tol_i64, so nothing
+ *              overflows anywhere in the int64 range; a float64 distance is
+ *              a double subtraction compared with tol_f64.
+ *   nearest:   both candidates, each after the tolerance; when both stand,
+ *              the backward one iff l - ron[pb] <= ron[pf] - l (a tie goes
+ *              backward), else whichever stands.
+ * out_idx[i] is the chosen POSITION IN THE SORTED RIGHT SIDE, or -1 for no
+ * match: an HF_INT64 column of lon's length, empty for an empty lon and all
+ * -1 for an empty ron.  All compares run in the column's own type; int64
+ * keys are never promoted to double (see hf_compare_scalar_i64).
+ *
+ * Device: with a by column, a grid-stride loop of one binary search per lane
+ * with the pair compare inlined, instantiated per (dtype, by or not,
+ * direction); nearest runs its second search only on rows that hit an equal
+ * right key.  Without one, both sides are ascending, so each workgroup takes
+ * 2048 consecutive left rows, bounds their contiguous right window with two
+ * global searches, copies a window of up to 2544 keys into LDS and searches
+ * there (a longer window is searched in place).  HF_ASOF_FORM=1 in the
+ * environment keeps calls without a by column on the general loop.
+ *
+ * HF_ERR_ARG: null lon/ron/out_idx, on columns of different or unsupported
+ * dtypes, a by column on one side only, a by column that is not int64 or
+ * not of its on column's length, a direction outside 0..2, has_tol with a
+ * negative (or NaN) tolerance. */
+enum { HF_ASOF_BACKWARD = 0, HF_ASOF_FORWARD = 1, HF_ASOF_NEAREST = 2 };
+
+int hf_asof_idx(const hf_col* lon, const hf_col* lby /* nullable */,
+                const hf_col* ron, const hf_col* rby /* nullable */,
+                int direction, int allow_exact,
+                int has_tol, int64_t tol_i64, double tol_f64,
+                hf_col** out_idx);
+
+/* Gather that tolerates "no match": out[i] = idx[i] < 0 ? fill : col[idx[i]]
+ * (the payload gather behind hf_asof_idx: NaN, code -1 or NaT in unmatched
+ * rows without padding the source).  col is HF_FLOAT64 (fill_f64 is used) or
+ * HF_INT64 (fill_i64 is used); *out has idx's length and col's dtype.  An
+ * idx entry >= col's length is the caller's bug, as in hf_gather.
+ *
+ * Device: one grid-stride pass, 16 B of streamed traffic per row plus the
+ * gathered read.
+ *
+ * HF_ERR_ARG: null col/idx/out, an idx that is not int64, an unsupported
+ * col dtype. */
+int hf_gather_fill(const hf_col* col, const hf_col* idx,
+                   double fill_f64, int64_t fill_i64, hf_col** out);
+
 /* Raw device-to-device copy on the hipframe stream — the interop bridge to
  * RCCL-visible torch buffers (exchange_splits): hf columns are copied into /
  * out of torch-allocated device tensors by address. */

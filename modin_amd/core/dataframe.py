@@ -3328,18 +3328,20 @@ class HipDataframe:
         part = HipDataframePartition(DeviceBlock(cols, n, cats))
         return HipDataframe([part], pandas.RangeIndex(n), names, [n], dts)
 
-    def merge_multi(self, other: "HipDataframe", on: list,
-                    how: str = "inner") -> "HipDataframe":
-        """Multi-key merge: fold the key columns of BOTH sides into ONE
-        int64 key with SHARED mins/strides (global over the union, so the
-        fold is consistent cross-frame; float keys ride the ordered
-        canonical-NaN transform first — NaN tuples match like pandas;
-        string keys recode into the left dictionary).  The right frame
-        drops its key columns (pandas on=[...] emits one set, from the
-        left), then the single-key engine runs on the fold and the
-        combined column drops from the result."""
+    def _fold_key_columns(self, other: "HipDataframe", lnames: list,
+                          rnames: list, ctx: str = "merge",
+                          single_plain: bool = False):
+        """Fold the key columns `lnames` of this frame and `rnames` of
+        `other` (paired by position) into ONE int64 code column per side,
+        each side concatenated over its partitions, with SHARED
+        mins/strides over both frames so equal key tuples get equal codes
+        and the code order is the lexicographic key order.  Float keys ride
+        the ordered canonical-NaN transform (NaN tuples match, as in
+        pandas), string keys recode into the left dictionary (right-only
+        categories become -2, never NaN's -1), wide spans densify through
+        the sorted distinct union.  `single_plain` returns a lone key's
+        encoded columns as they are, without the min shift."""
         from .. import distributed as dist_mod
-        KEY = "\x00mkey\x00"
         lcats = (self._partitions[0].block().cats
                  if self._partitions else {})
         rcats = (other._partitions[0].block().cats
@@ -3350,28 +3352,31 @@ class HipDataframe:
             return cs[0] if len(cs) == 1 else lib.concat(cs)
 
         mins, spans, enc_l, enc_r = [], [], [], []
-        for b in on:
-            if b not in self.columns or b not in other.columns:
-                raise lib.HfError(f"merge: key column {b!r} missing")
-            if (b in lcats) != (b in rcats):
-                raise lib.HfError("merge: key column is a string on one "
+        for b, rb in zip(lnames, rnames):
+            if b not in self.columns or rb not in other.columns:
+                miss = b if b not in self.columns else rb
+                raise lib.HfError(f"{ctx}: key column {miss!r} missing")
+            if (b in lcats) != (rb in rcats):
+                raise lib.HfError(f"{ctx}: key column is a string on one "
                                   "side only")
-            lc, rc = concat_col(self, b), concat_col(other, b)
+            lc, rc = concat_col(self, b), concat_col(other, rb)
             if b in lcats:
-                if not rcats[b].equals(lcats[b]):
-                    rc = recode_dict_col(rc, rcats[b], lcats[b],
+                if not rcats[rb].equals(lcats[b]):
+                    rc = recode_dict_col(rc, rcats[rb], lcats[b],
                                          missing=-2)
                 # shift codes so -2/-1 fold like ordinary keys
                 lo = -2
                 lc2, rc2 = lc, rc
             elif (self.dtypes[b] == np.dtype(np.float64)
-                  or other.dtypes[b] == np.dtype(np.float64)):
+                  or other.dtypes[rb] == np.dtype(np.float64)):
                 lc2 = lib.ordered_i64(lib.cast_f64(lc))
                 rc2 = lib.ordered_i64(lib.cast_f64(rc))
                 lo = None
             else:
                 lc2, rc2 = lc, rc
                 lo = None
+            if single_plain and len(lnames) == 1:
+                return lc2, rc2
             mn = mx = None
             for c in (lc2, rc2):
                 if c.length:
@@ -3403,11 +3408,11 @@ class HipDataframe:
             total *= sp
             if total > (1 << 62):
                 raise lib.HfError(
-                    "merge: combined key range of "
-                    f"{on} exceeds 2^62 (hashed multi-key merge is a "
-                    "later round)")
-        strides = [1] * len(on)
-        for i in range(len(on) - 2, -1, -1):
+                    f"{ctx}: combined key range of "
+                    f"{list(lnames)} exceeds 2^62 (hashed multi-key {ctx} "
+                    "is a later round)")
+        strides = [1] * len(lnames)
+        for i in range(len(lnames) - 2, -1, -1):
             strides[i] = strides[i + 1] * spans[i + 1]
 
         def fold(cols):
@@ -3419,6 +3424,26 @@ class HipDataframe:
                 comb = t if comb is None else lib.binary(lib.BIN_ADD,
                                                          comb, t)
             return comb
+
+        return fold(enc_l), fold(enc_r)
+
+    def merge_multi(self, other: "HipDataframe", on: list,
+                    how: str = "inner") -> "HipDataframe":
+        """Multi-key merge: fold the key columns of BOTH sides into ONE
+        int64 key with SHARED mins/strides (global over the union, so the
+        fold is consistent cross-frame; float keys ride the ordered
+        canonical-NaN transform first — NaN tuples match like pandas;
+        string keys recode into the left dictionary).  The right frame
+        drops its key columns (pandas on=[...] emits one set, from the
+        left), then the single-key engine runs on the fold and the
+        combined column drops from the result."""
+        KEY = "\x00mkey\x00"
+
+        def concat_col(frame, name):
+            cs = [p.block().columns[name] for p in frame._partitions]
+            return cs[0] if len(cs) == 1 else lib.concat(cs)
+
+        lcode, rcode = self._fold_key_columns(other, on, on)
 
         def with_key(frame, comb, drop_keys):
             names = [c for c in frame.columns
@@ -3437,12 +3462,235 @@ class HipDataframe:
                 pandas.RangeIndex(n), names + [KEY], [n],
                 pandas.Series(dts))
 
-        L = with_key(self, fold(enc_l), drop_keys=False)
-        R = with_key(other, fold(enc_r), drop_keys=True)
+        L = with_key(self, lcode, drop_keys=False)
+        R = with_key(other, rcode, drop_keys=True)
         res = L.broadcast_join(R, KEY, how)
         keep = [c for c in res.columns if c != KEY]
         out = res.take_columns(keep)
         return out
+
+    # ---- merge_asof (the reference defaults to pandas:
+    #      storage_formats/base/query_compiler.py:1713) ----
+    def _asof_check_on(self, name: str, side: str) -> None:
+        """pandas' demand on an as-of key column: no null, ascending.
+        Device reduces only; one boolean per test reaches the host."""
+        cols = [p.block().columns[name] for p in self._partitions]
+        is_f = self.dtypes[name] == np.dtype(np.float64)
+        if is_f:
+            null = any(lib.reduce(c).count < c.length for c in cols)
+        else:
+            null = name in self._dt_cols() and self._col_has_nat(name)
+        if null:
+            raise ValueError(f"Merge keys contain null values on {side} side")
+        prev = None
+        ok = True
+        for c in cols:
+            if not c.length:
+                continue
+            r = lib.reduce(c)
+            lo, hi = (r.mn, r.mx) if is_f else (r.imn, r.imx)
+            if prev is not None and lo < prev:
+                ok = False
+            prev = hi
+            if c.length > 1:
+                a = lib.col_slice(c, 0, c.length - 1)
+                b = lib.col_slice(c, 1, c.length - 1)
+                if is_f:
+                    d = lib.reduce(lib.binary(lib.BIN_SUB, b, a))
+                    ok = ok and not (d.count and d.mn < 0)
+                else:
+                    # max(a, b) - b is zero exactly where a <= b: the
+                    # difference may wrap but only a == b gives zero
+                    d = lib.reduce(lib.binary(
+                        lib.BIN_SUB, lib.binary(lib.BIN_MAX, a, b), b))
+                    ok = ok and d.imn == 0 and d.imx == 0
+            if not ok:
+                raise ValueError(f"{side} keys must be sorted")
+
+    def asof_join(self, other: "HipDataframe", left_on, right_on,
+                  left_by=None, right_by=None, suffixes=("_x", "_y"),
+                  tolerance=None, allow_exact_matches: bool = True,
+                  direction: str = "backward", left_index: bool = False,
+                  right_index: bool = False) -> "HipDataframe":
+        """pandas.merge_asof: every left row keeps its place and takes the
+        payload of ONE right row — the last at or before its `on` key
+        (backward), the first at or after (forward) or the closer of the two
+        (nearest) — among the right rows with the same `by` tuple.  The
+        match runs on device (hf_asof_idx over the (by code, on)-sorted right
+        side), the payload rides hf_gather_fill, so unmatched rows get NaN /
+        code -1 / NaT without padding anything."""
+        from pandas.errors import MergeError
+        from pandas.api.types import is_integer, is_number
+        from ..distributed import is_active
+        if left_index or right_index:
+            raise lib.HfError("merge_asof: left_index/right_index is a later "
+                              "round (reset_index() and pass on=)")
+        if is_active():
+            raise lib.HfError("merge_asof: world>1 is a later round")
+        if direction not in ("backward", "forward", "nearest"):
+            raise MergeError(f"direction invalid: {direction}")
+        if not isinstance(allow_exact_matches, (bool, np.bool_)):
+            raise MergeError("allow_exact_matches must be boolean, "
+                             f"passed {allow_exact_matches}")
+
+        def one_key(v, side):
+            if isinstance(v, (list, tuple)):
+                if len(v) != 1:
+                    raise MergeError(f"can only asof on a key for {side}")
+                return v[0]
+            return v
+
+        left_on, right_on = one_key(left_on, "left"), one_key(right_on,
+                                                              "right")
+        if left_by is None and right_by is not None:
+            raise MergeError("missing left_by")
+        if left_by is not None and right_by is None:
+            raise MergeError("missing right_by")
+        if left_by is not None:
+            left_by = (list(left_by) if isinstance(left_by, (list, tuple))
+                       else [left_by])
+            right_by = (list(right_by) if isinstance(right_by, (list, tuple))
+                        else [right_by])
+            if len(left_by) != len(right_by):
+                raise MergeError(
+                    "left_by and right_by must be the same length")
+        else:
+            left_by, right_by = [], []
+        for c in [left_on] + left_by:
+            if c not in self.columns:
+                raise lib.HfError(
+                    f"merge_asof: left frame has no column {c!r}")
+        for c in [right_on] + right_by:
+            if c not in other.columns:
+                raise lib.HfError(
+                    f"merge_asof: right frame has no column {c!r}")
+        lcats = (self._partitions[0].block().cats
+                 if self._partitions else {})
+        rcats = (other._partitions[0].block().cats
+                 if other._partitions else {})
+        lo_dt, ro_dt = self.dtypes[left_on], other.dtypes[right_on]
+        if left_on in lcats or right_on in rcats:
+            raise MergeError(
+                f"Incompatible merge dtype, {ro_dt!r} and {lo_dt!r}, both "
+                "sides must have numeric dtype")
+        for i, (lc, rc) in enumerate(zip(left_by + [left_on],
+                                         right_by + [right_on])):
+            if self.dtypes[lc] != other.dtypes[rc]:
+                raise MergeError(
+                    f"incompatible merge keys [{i}] {self.dtypes[lc]!r} and "
+                    f"{other.dtypes[rc]!r}, must be the same type")
+        on_dt = left_on in self._dt_cols()
+        tol = None
+        if tolerance is not None:
+            import datetime
+            msg = (f"incompatible tolerance {tolerance}, must be compat "
+                   f"with type {lo_dt!r}")
+            if on_dt:
+                if not isinstance(tolerance, datetime.timedelta):
+                    raise MergeError(msg)
+                tol = int(pandas.Timedelta(tolerance).as_unit("ns").value)
+            elif lo_dt == np.dtype(np.int64):
+                if not is_integer(tolerance):
+                    raise MergeError(msg)
+                tol = int(tolerance)
+            else:
+                if not is_number(tolerance):
+                    raise MergeError(msg)
+                tol = float(tolerance)
+            if tol < 0:
+                raise MergeError("tolerance must be positive")
+        if not isinstance(suffixes, (list, tuple)) or len(suffixes) != 2:
+            raise TypeError(
+                f"Passing 'suffixes' as a {type(suffixes)}, is not "
+                "supported. Provide 'suffixes' as a tuple instead.")
+        self._asof_check_on(left_on, "left")
+        other._asof_check_on(right_on, "right")
+
+        # ---- output names: left columns, then right payload ----
+        r_drop = {rc for lc, rc in zip(left_by + [left_on],
+                                       right_by + [right_on]) if lc == rc}
+        right_names = [c for c in other.columns if c not in r_drop]
+        overlap = set(self.columns) & set(right_names)
+        lsuf, rsuf = suffixes
+        if overlap and not lsuf and not rsuf:
+            raise ValueError("columns overlap but no suffix specified: "
+                             f"{pandas.Index(sorted(overlap))}")
+        lout = {c: (f"{c}{lsuf}" if c in overlap and lsuf else c)
+                for c in self.columns}
+        rout = {c: (f"{c}{rsuf}" if c in overlap and rsuf else c)
+                for c in right_names}
+        out_columns = ([lout[c] for c in self.columns]
+                       + [rout[c] for c in right_names])
+        dup = {c for c in out_columns if out_columns.count(c) > 1}
+        if dup:
+            raise MergeError("Passing 'suffixes' which cause duplicate "
+                             f"columns {dup} is not allowed.")
+
+        def concat_col(frame, name):
+            cs = [p.block().columns[name] for p in frame._partitions]
+            return cs[0] if len(cs) == 1 else lib.concat(cs)
+
+        # ---- right side: (by code, on) order ----
+        ron = concat_col(other, right_on)
+        perm = rby = lby_all = None
+        if left_by:
+            lby_all, rcode = self._fold_key_columns(
+                other, left_by, right_by, ctx="merge_asof",
+                single_plain=True)
+            perm = lib.sort_perm(rcode)  # stable: on stays ascending
+            rby = lib.gather(rcode, perm)
+            ron = lib.gather(ron, perm)
+        dir_code = {"backward": lib.ASOF_BACKWARD,
+                    "forward": lib.ASOF_FORWARD,
+                    "nearest": lib.ASOF_NEAREST}[direction]
+
+        # ---- probe every left partition; the dtype rule needs all of them
+        ridxs, off, any_unmatched = [], 0, False
+        for p in self._partitions:
+            block = p.block()
+            lby = (lib.col_slice(lby_all, off, block.length)
+                   if left_by and len(self._partitions) > 1 else lby_all)
+            off += block.length
+            pos = lib.asof_idx(block.columns[left_on], lby, ron, rby,
+                               dir_code, bool(allow_exact_matches), tol)
+            ridx = pos if perm is None else lib.gather_fill(perm, pos, -1)
+            if block.length and lib.reduce(ridx).imn < 0:
+                any_unmatched = True
+            ridxs.append(ridx)
+
+        # ---- payload: gather with the fill of the column's kind ----
+        r_dtc = other._dt_cols()
+        rsrc, rfill, dtypes = {}, {}, {}
+        for c in self.columns:
+            dtypes[lout[c]] = self.dtypes[c]
+        for c in right_names:
+            col, d = concat_col(other, c), other.dtypes[c]
+            if c in rcats:
+                fill = -1
+            elif c in r_dtc:
+                fill = INAT
+            elif col.dtype_code == lib.HF_INT64:
+                fill = 0  # never used: no row is unmatched
+                if any_unmatched:
+                    col, d, fill = (lib.cast_f64(col), np.dtype(np.float64),
+                                    float("nan"))
+            else:
+                fill = float("nan")
+            rsrc[c], rfill[c], dtypes[rout[c]] = col, fill, d
+        out_cats = {lout[c]: v for c, v in lcats.items() if c in lout}
+        out_cats.update({rout[c]: v for c, v in rcats.items() if c in rout})
+        out_parts, lengths = [], []
+        for p, ridx in zip(self._partitions, ridxs):
+            block = p.block()
+            cols = {lout[c]: block.columns[c] for c in self.columns}
+            for c in right_names:
+                cols[rout[c]] = lib.gather_fill(rsrc[c], ridx, rfill[c])
+            out_parts.append(HipDataframePartition(
+                DeviceBlock(cols, block.length, dict(out_cats))))
+            lengths.append(block.length)
+        total = sum(lengths)
+        return HipDataframe(out_parts, pandas.RangeIndex(total), out_columns,
+                            lengths, pandas.Series(dtypes, dtype=object))
 
     def _binned_merge(self, other: "HipDataframe", on: str, how: str,
                       key_f64: bool, n_bins: int = 0) -> "HipDataframe":

@@ -192,6 +192,13 @@ def load() -> ct.CDLL:
                                          ct.POINTER(ct.c_int64)]),
             "hf_gather": (ct.c_int, [ct.c_void_p, ct.c_void_p,
                                      ct.POINTER(ct.c_void_p)]),
+            "hf_gather_fill": (ct.c_int, [ct.c_void_p, ct.c_void_p,
+                                          ct.c_double, ct.c_int64,
+                                          ct.POINTER(ct.c_void_p)]),
+            "hf_asof_idx": (ct.c_int, [ct.c_void_p, ct.c_void_p, ct.c_void_p,
+                                       ct.c_void_p, ct.c_int, ct.c_int,
+                                       ct.c_int, ct.c_int64, ct.c_double,
+                                       ct.POINTER(ct.c_void_p)]),
             "hf_compare_scalar": (ct.c_int, [ct.c_int, ct.c_void_p,
                                              ct.c_double,
                                              ct.POINTER(ct.c_void_p)]),
@@ -236,7 +243,8 @@ def exported_symbols():
         "hf_search_sorted", "hf_ordered_i64", "hf_cumsum", "hf_seg_cumsum",
         "hf_ewm_mean", "hf_scatter", "hf_cross_idx",
         "hf_col_concat", "hf_col_slice", "hf_join_build", "hf_join_free", "hf_join_probe",
-        "hf_gather", "hf_compare_scalar", "hf_compare_scalar_i64",
+        "hf_gather", "hf_gather_fill", "hf_asof_idx",
+        "hf_compare_scalar", "hf_compare_scalar_i64",
         "hf_filter_plan", "hf_filter_apply",
         "hf_filter_iota", "hf_filter_plan_free", "hf_profiling",
         "hf_kernel_stats", "hf_kernel_stats_reset",
@@ -879,6 +887,44 @@ def gather(col: ColumnRef, idx: ColumnRef) -> ColumnRef:
     out = ct.c_void_p()
     _check(load().hf_gather(col.handle, idx.handle, ct.byref(out)), "hf_gather")
     return _wrap(out, idx.length, col.dtype_code)
+
+
+def gather_fill(col: ColumnRef, idx: ColumnRef, fill) -> ColumnRef:
+    """out[i] = fill where idx[i] < 0, else col[idx[i]] (hf_gather_fill);
+    `fill` is read as a float for a float64 column and as an int for an
+    int64 one."""
+    ensure_ready()
+    out = ct.c_void_p()
+    is_f = col.dtype_code == HF_FLOAT64
+    _check(load().hf_gather_fill(col.handle, idx.handle,
+                                 float(fill) if is_f else 0.0,
+                                 0 if is_f else int(fill), ct.byref(out)),
+           "hf_gather_fill")
+    return _wrap(out, idx.length, col.dtype_code)
+
+
+# hf_asof_idx directions (include/hipframe.h)
+ASOF_BACKWARD, ASOF_FORWARD, ASOF_NEAREST = range(3)
+
+
+def asof_idx(lon: ColumnRef, lby, ron: ColumnRef, rby, direction: int,
+             allow_exact: bool = True, tolerance=None) -> ColumnRef:
+    """Per left row, the position in the (rby, ron)-sorted right side of its
+    as-of match, or -1 (hf_asof_idx).  lby/rby are both None or both int64
+    columns; tolerance None means unbounded, else an int for int64 `on`
+    columns and a float for float64 ones."""
+    ensure_ready()
+    out = ct.c_void_p()
+    has_tol = tolerance is not None
+    is_f = lon.dtype_code == HF_FLOAT64
+    _check(load().hf_asof_idx(
+        lon.handle, None if lby is None else lby.handle,
+        ron.handle, None if rby is None else rby.handle,
+        int(direction), 1 if allow_exact else 0, 1 if has_tol else 0,
+        int(tolerance) if has_tol and not is_f else 0,
+        float(tolerance) if has_tol and is_f else 0.0,
+        ct.byref(out)), "hf_asof_idx")
+    return _wrap(out, lon.length, HF_INT64)
 
 
 def sync() -> None:

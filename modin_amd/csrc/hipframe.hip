@@ -2805,6 +2805,199 @@ __global__ void __launch_bounds__(BLOCK) k_gather_i64(
   for (; i < n; i += stride) out[i] = src[idx[i]];
 }
 
+template <typename T>
+__global__ void __launch_bounds__(BLOCK) k_gather_fill(
+    const T* __restrict__ src, const int64_t* __restrict__ idx, T fill,
+    T* __restrict__ out, int64_t n) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (; i < n; i += stride) {
+    const int64_t j = idx[i];
+    out[i] = j < 0 ? fill : src[j];
+  }
+}
+
+// ---------------------------------------------------------------------------
+// As-of probe (pandas merge_asof; hf_asof_idx in the header states the row
+// contract).  The right side is ascending in the pair order (rby, ron); each
+// left row (b, l) runs one bound search in that order and keeps the position
+// next to the bound, fenced to its own group and to the tolerance.  Every
+// compare is in the column's own type: int64 keys are never promoted, and
+// an int64 distance is the unsigned difference of the ordered pair.
+// ---------------------------------------------------------------------------
+template <typename T> struct AsofDist;
+template <> struct AsofDist<int64_t> {
+  using type = unsigned long long;
+  // hi >= lo
+  static __device__ __forceinline__ type of(int64_t hi, int64_t lo) {
+    return (type)hi - (type)lo;
+  }
+};
+template <> struct AsofDist<double> {
+  using type = double;
+  static __device__ __forceinline__ type of(double hi, double lo) {
+    return hi - lo;
+  }
+};
+
+// First p in [lo, hi) whose pair is >= (b, l) (upper = false) or > (b, l)
+// (upper = true); hi when there is none.
+template <typename T, bool HAS_BY>
+__device__ __forceinline__ int64_t asof_bound(
+    const int64_t* __restrict__ rby, const T* __restrict__ ron, int64_t lo,
+    int64_t hi, int64_t b, T l, bool upper) {
+  while (lo < hi) {  // the first levels stay L2-resident
+    const int64_t mid = (lo + hi) >> 1;
+    const T r = ron[mid];
+    bool below = (r < l) | (upper & (r == l));
+    if (HAS_BY) {
+      const int64_t gb = rby[mid];
+      below = (gb < b) | ((gb == b) & below);
+    }
+    if (below) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+template <typename T, bool HAS_BY>
+__device__ __forceinline__ bool asof_is_key(
+    const int64_t* __restrict__ rby, const T* __restrict__ ron, int64_t p,
+    int64_t b, T l) {
+  return ron[p] == l && (!HAS_BY || rby[p] == b);
+}
+
+// One left row.  `first` is the bound the direction needs (backward: upper
+// bound when exact matches count, else lower; forward the other way round).
+// The opposite bound, which only nearest needs, differs from it only across
+// a run of right rows equal to (b, l), so it costs a second search on exact
+// hits alone.
+template <typename T, bool HAS_BY, int DIR>
+__device__ __forceinline__ int64_t asof_row(
+    const int64_t* __restrict__ rby, const T* __restrict__ ron, int64_t m,
+    int64_t b, T l, bool allow_exact, bool has_tol,
+    typename AsofDist<T>::type tol) {
+  using D = AsofDist<T>;
+  int64_t ub_or_lb_back, lb_or_ub_fwd;  // backward: bound - 1; forward: bound
+  if (DIR == HF_ASOF_BACKWARD) {
+    ub_or_lb_back = asof_bound<T, HAS_BY>(rby, ron, 0, m, b, l, allow_exact);
+    lb_or_ub_fwd = m;
+  } else if (DIR == HF_ASOF_FORWARD) {
+    lb_or_ub_fwd = asof_bound<T, HAS_BY>(rby, ron, 0, m, b, l, !allow_exact);
+    ub_or_lb_back = 0;
+  } else if (allow_exact) {
+    // backward wants the upper bound, forward the lower
+    const int64_t ub = asof_bound<T, HAS_BY>(rby, ron, 0, m, b, l, true);
+    ub_or_lb_back = ub;
+    lb_or_ub_fwd = ub;
+    if (ub > 0 && asof_is_key<T, HAS_BY>(rby, ron, ub - 1, b, l))
+      lb_or_ub_fwd = asof_bound<T, HAS_BY>(rby, ron, 0, ub - 1, b, l, false);
+  } else {
+    // backward wants the lower bound, forward the upper
+    const int64_t lb = asof_bound<T, HAS_BY>(rby, ron, 0, m, b, l, false);
+    ub_or_lb_back = lb;
+    lb_or_ub_fwd = lb;
+    if (lb < m && asof_is_key<T, HAS_BY>(rby, ron, lb, b, l))
+      lb_or_ub_fwd = asof_bound<T, HAS_BY>(rby, ron, lb + 1, m, b, l, true);
+  }
+  int64_t pb = -1, pf = -1;
+  typename D::type db = 0, df = 0;
+  if (DIR != HF_ASOF_FORWARD) {
+    const int64_t p = ub_or_lb_back - 1;
+    if (p >= 0 && (!HAS_BY || rby[p] == b)) {
+      db = D::of(l, ron[p]);
+      if (!has_tol || !(db > tol)) pb = p;
+    }
+  }
+  if (DIR != HF_ASOF_BACKWARD) {
+    const int64_t p = lb_or_ub_fwd;
+    if (p < m && (!HAS_BY || rby[p] == b)) {
+      df = D::of(ron[p], l);
+      if (!has_tol || !(df > tol)) pf = p;
+    }
+  }
+  if (DIR == HF_ASOF_BACKWARD) return pb;
+  if (DIR == HF_ASOF_FORWARD) return pf;
+  if (pb >= 0 && pf >= 0) return db <= df ? pb : pf;  // a tie goes backward
+  return pb >= 0 ? pb : pf;
+}
+
+template <typename T, bool HAS_BY, int DIR>
+__global__ void __launch_bounds__(BLOCK) k_asof_idx(
+    const T* __restrict__ lon, const int64_t* __restrict__ lby, int64_t n,
+    const T* __restrict__ ron, const int64_t* __restrict__ rby, int64_t m,
+    int allow_exact, int has_tol, typename AsofDist<T>::type tol,
+    int64_t* __restrict__ out) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (; i < n; i += stride)
+    out[i] = asof_row<T, HAS_BY, DIR>(rby, ron, m, HAS_BY ? lby[i] : 0,
+                                      lon[i], allow_exact != 0, has_tol != 0,
+                                      tol);
+}
+
+// Sorted-left form: no by column and lon ascending, so the ASOF_TILE
+// consecutive left rows of a block can only match inside one contiguous right
+// window.  Two global searches (the tile's first and last key) bound it, one
+// position wider on each side for the backward candidate below the first key
+// and the forward candidate above the last.  A window of at most ASOF_WIN
+// keys is copied into LDS with coalesced loads and every row searches there;
+// a longer one is searched in place, which is still a far shorter range than
+// m.  Rows go to lanes strided by BLOCK: a wave's 64 lanes hold 64
+// consecutive rows, so the left loads and the result stores coalesce with no
+// staging and neighbouring lanes walk nearly the same search path.
+// An lon that is not ascending gives wrong positions but no wild read: every
+// search stays inside [w_lo, w_hi), itself clamped to [0, m].
+constexpr int ASOF_TILE = 2048;
+constexpr int ASOF_PER = ASOF_TILE / BLOCK;
+constexpr int ASOF_WIN = 2544;  // with s_w just under 20 KiB of LDS, so
+                                // 8 workgroups (8 waves/SIMD) fit a CU
+
+template <typename T, int DIR>
+__global__ void __launch_bounds__(BLOCK) k_asof_idx_sorted(
+    const T* __restrict__ lon, int64_t n, const T* __restrict__ ron,
+    int64_t m, int allow_exact, int has_tol, typename AsofDist<T>::type tol,
+    int64_t* __restrict__ out) {
+  __shared__ T s_win[ASOF_WIN];
+  __shared__ int64_t s_w[2];
+  const int64_t t0 = (int64_t)blockIdx.x * ASOF_TILE;
+  const int64_t t1 = min(t0 + (int64_t)ASOF_TILE, n);
+  T lv[ASOF_PER];
+#pragma unroll
+  for (int j = 0; j < ASOF_PER; ++j) {
+    const int64_t i = t0 + (int64_t)j * BLOCK + threadIdx.x;
+    lv[j] = i < t1 ? lon[i] : T{};
+  }
+  // one lane of two different waves each runs one of the bounding searches
+  if (threadIdx.x == 0)
+    s_w[0] = max(asof_bound<T, false>(nullptr, ron, 0, m, 0, lon[t0], false)
+                     - 1, (int64_t)0);
+  if (threadIdx.x == 64)
+    s_w[1] = min(asof_bound<T, false>(nullptr, ron, 0, m, 0, lon[t1 - 1],
+                                      true) + 1, m);
+  __syncthreads();
+  const int64_t w_lo = s_w[0];
+  const int64_t wn = s_w[1] - w_lo;
+  const bool in_lds = wn <= ASOF_WIN;  // uniform over the block
+  if (in_lds) {
+    for (int j = threadIdx.x; j < wn; j += BLOCK) s_win[j] = ron[w_lo + j];
+    __syncthreads();
+  }
+#pragma unroll
+  for (int j = 0; j < ASOF_PER; ++j) {
+    const int64_t i = t0 + (int64_t)j * BLOCK + threadIdx.x;
+    if (i < t1) {
+      const int64_t p =
+          in_lds ? asof_row<T, false, DIR>(nullptr, s_win, wn, 0, lv[j],
+                                           allow_exact != 0, has_tol != 0,
+                                           tol)
+                 : asof_row<T, false, DIR>(nullptr, ron + w_lo, wn, 0, lv[j],
+                                           allow_exact != 0, has_tol != 0,
+                                           tol);
+      out[i] = p < 0 ? -1 : p + w_lo;
+    }
+  }
+}
+
 // Cross-join row indices: lidx[i] = i / nr, ridx[i] = i % nr — the gather
 // indices materializing a cartesian product (pandas merge how='cross').
 __global__ void __launch_bounds__(BLOCK) k_cross_idx(
@@ -5332,6 +5525,102 @@ int hf_gather(const hf_col* col, const hf_col* idx, hf_col** out) {
                          (const int64_t*)idx->dptr, o.data<int64_t>(), n);
   });
   return o.commit_if(rc, out);
+}
+
+int hf_gather_fill(const hf_col* col, const hf_col* idx, double fill_f64,
+                   int64_t fill_i64, hf_col** out) {
+  HF_NEED_INIT("hf_gather_fill");
+  if (!col || !idx || !out)
+    return set_err(HF_ERR_ARG, "hf_gather_fill", "null");
+  if (idx->dtype != HF_INT64)
+    return set_err(HF_ERR_ARG, "hf_gather_fill", "index must be int64");
+  if (col->dtype != HF_FLOAT64 && col->dtype != HF_INT64)
+    return set_err(HF_ERR_ARG, "hf_gather_fill", "col must be f64 or i64");
+  const int64_t n = idx->len;
+  ColOut o;
+  int rc = o.alloc(n, col->dtype);
+  if (rc != HF_OK) return rc;
+  if (n == 0) { o.commit(out); return HF_OK; }
+  rc = with_dtype(col->dtype, [&](auto tTag) {
+    using T = decltype(tTag);
+    const T fill = std::is_same<T, double>::value ? (T)fill_f64 : (T)fill_i64;
+    return timed_launch("gather_fill", [&] {
+      hipLaunchKernelGGL((k_gather_fill<T>), dim3((uint32_t)grid_for(n)),
+                         dim3(BLOCK), 0, g.stream, (const T*)col->dptr,
+                         (const int64_t*)idx->dptr, fill, o.data<T>(), n);
+    });
+  });
+  return o.commit_if(rc, out);
+}
+
+int hf_asof_idx(const hf_col* lon, const hf_col* lby, const hf_col* ron,
+                const hf_col* rby, int direction, int allow_exact,
+                int has_tol, int64_t tol_i64, double tol_f64,
+                hf_col** out_idx) {
+  HF_NEED_INIT("hf_asof_idx");
+  if (!lon || !ron || !out_idx)
+    return set_err(HF_ERR_ARG, "hf_asof_idx", "null");
+  if (lon->dtype != ron->dtype ||
+      (lon->dtype != HF_INT64 && lon->dtype != HF_FLOAT64))
+    return set_err(HF_ERR_ARG, "hf_asof_idx",
+                   "on columns must both be int64 or both float64");
+  if ((lby == nullptr) != (rby == nullptr))
+    return set_err(HF_ERR_ARG, "hf_asof_idx", "by column on one side only");
+  if (lby && (lby->dtype != HF_INT64 || rby->dtype != HF_INT64 ||
+              lby->len != lon->len || rby->len != ron->len))
+    return set_err(HF_ERR_ARG, "hf_asof_idx",
+                   "by columns must be int64 of their on column's length");
+  if (direction < HF_ASOF_BACKWARD || direction > HF_ASOF_NEAREST)
+    return set_err(HF_ERR_ARG, "hf_asof_idx", "direction must be 0, 1 or 2");
+  if (has_tol && (lon->dtype == HF_INT64 ? tol_i64 < 0 : !(tol_f64 >= 0.0)))
+    return set_err(HF_ERR_ARG, "hf_asof_idx", "tolerance must be >= 0");
+  const int64_t n = lon->len, m = ron->len;
+  ColOut o;
+  int rc = o.alloc(n, HF_INT64);
+  if (rc != HF_OK) return rc;
+  if (n == 0) { o.commit(out_idx); return HF_OK; }
+  // Without a by column lon is ascending (the contract), which is what the
+  // sorted-left form needs.  HF_ASOF_FORM=1 keeps such calls on the general
+  // form (measurements, and the tests that compare the two).
+  const char* form = getenv("HF_ASOF_FORM");
+  const bool sorted_form = !lby && !(form && form[0] == '1');
+  auto with_dir = [&](auto&& f) {
+    return direction == HF_ASOF_BACKWARD  ? f(int_tag<HF_ASOF_BACKWARD>{})
+           : direction == HF_ASOF_FORWARD ? f(int_tag<HF_ASOF_FORWARD>{})
+                                          : f(int_tag<HF_ASOF_NEAREST>{});
+  };
+  rc = with_dtype(lon->dtype, [&](auto tTag) {
+    using T = decltype(tTag);
+    using D = typename AsofDist<T>::type;
+    const D tol = std::is_same<T, double>::value ? (D)tol_f64 : (D)tol_i64;
+    return with_bool(lby != nullptr, [&](auto bTag) {
+      constexpr bool B = decltype(bTag)::value;
+      const int64_t* lb = B ? (const int64_t*)lby->dptr : nullptr;
+      const int64_t* rb = B ? (const int64_t*)rby->dptr : nullptr;
+      return with_dir([&](auto dTag) {
+        constexpr int DIR = decltype(dTag)::value;
+        if constexpr (!B) {
+          if (sorted_form)
+            return timed_launch("asof_idx", [&] {
+              hipLaunchKernelGGL(
+                  (k_asof_idx_sorted<T, DIR>),
+                  dim3((uint32_t)((n + ASOF_TILE - 1) / ASOF_TILE)),
+                  dim3(BLOCK), 0, g.stream, (const T*)lon->dptr, n,
+                  (const T*)ron->dptr, m, allow_exact, has_tol, tol,
+                  o.data<int64_t>());
+            });
+        }
+        return timed_launch("asof_idx", [&] {
+          hipLaunchKernelGGL((k_asof_idx<T, B, DIR>),
+                             dim3((uint32_t)grid_for(n)), dim3(BLOCK), 0,
+                             g.stream, (const T*)lon->dptr, lb, n,
+                             (const T*)ron->dptr, rb, m, allow_exact, has_tol,
+                             tol, o.data<int64_t>());
+        });
+      });
+    });
+  });
+  return o.commit_if(rc, out_idx);
 }
 
 // The digit-offset part of one radix pass, shared by the narrow and the wide

@@ -35,7 +35,8 @@ from ..core import lib
 from ..core.lib import HfError as HfErrorProxy
 from ..query_compiler import HipQueryCompiler
 
-__all__ = ["DataFrame", "Series", "concat", "merge", "from_pandas"]
+__all__ = ["DataFrame", "Series", "concat", "merge", "merge_asof",
+           "from_pandas"]
 
 
 def read_parquet(path, columns=None):
@@ -129,6 +130,44 @@ def concat(objs, ignore_index: bool = False, axis=0):
 def merge(left: "DataFrame", right: "DataFrame", **kwargs) -> "DataFrame":
     """Module-level pandas.merge form."""
     return left.merge(right, **kwargs)
+
+
+def merge_asof(left: "DataFrame", right: "DataFrame", on=None, left_on=None,
+               right_on=None, left_index: bool = False,
+               right_index: bool = False, by=None, left_by=None,
+               right_by=None, suffixes=("_x", "_y"), tolerance=None,
+               allow_exact_matches: bool = True,
+               direction: str = "backward") -> "DataFrame":
+    """pandas.merge_asof: a left join on the nearest `on` key instead of an
+    equal one, optionally inside equal `by` groups.  Both frames must be
+    sorted by their `on` column."""
+    if not isinstance(left, DataFrame) or not isinstance(right, DataFrame):
+        bad = right if isinstance(left, DataFrame) else left
+        raise ValueError(
+            f"can not merge DataFrame with instance of type {type(bad)}")
+    # the index flags exclude the column forms of the same side's key
+    if ((on and (left_index or right_index)) or (left_on and left_index)
+            or (right_on and right_index)):
+        raise ValueError(
+            "Can't combine left/right_index with left/right_on or on.")
+    if on is not None:
+        if left_on is not None or right_on is not None:
+            raise ValueError(
+                "If 'on' is set, 'left_on' and 'right_on' can't be set.")
+        left_on = right_on = on
+    if by is not None:
+        if left_by is not None or right_by is not None:
+            raise ValueError(
+                "Can't have both 'by' and 'left_by' or 'right_by'")
+        left_by = right_by = by
+    if left_on is None and not left_index:
+        raise ValueError("Must pass on, left_on, or left_index=True")
+    if right_on is None and not right_index:
+        raise ValueError("Must pass on, right_on, or right_index=True")
+    return DataFrame(query_compiler=left._query_compiler.merge_asof(
+        right._query_compiler, left_on, right_on, left_index, right_index,
+        left_by, right_by, suffixes, tolerance, allow_exact_matches,
+        direction))
 
 
 def to_datetime(arg, format=None, errors: str = "raise"):  # noqa: A002

@@ -1064,6 +1064,20 @@ class HipQueryCompiler:
             self._modin_frame.broadcast_join(right._modin_frame, on, how)
         )
 
+    # ---- merge_asof (the reference's base query compiler defaults to
+    #      pandas, storage_formats/base/query_compiler.py:1713; the argument
+    #      order is the reference's) ----
+    def merge_asof(self, right: "HipQueryCompiler", left_on, right_on,
+                   left_index: bool = False, right_index: bool = False,
+                   left_by=None, right_by=None, suffixes=("_x", "_y"),
+                   tolerance=None, allow_exact_matches: bool = True,
+                   direction: str = "backward") -> "HipQueryCompiler":
+        return self.__constructor__(self._modin_frame.asof_join(
+            right._modin_frame, left_on, right_on, left_by=left_by,
+            right_by=right_by, suffixes=suffixes, tolerance=tolerance,
+            allow_exact_matches=allow_exact_matches, direction=direction,
+            left_index=left_index, right_index=right_index))
+
     # ---- column assignment (reference qc.setitem / insert,
     #      storage_formats/pandas/query_compiler.py setitem_builder) ----
     def write_column(self, name: str,
