@@ -71,13 +71,22 @@ struct GbKeyCache {
   // (k_gb_replay).  One plan per column, valid for exactly
   // (plan_kmin, plan_nslots, plan_rl) at GB_PLAN_TILE rows per tile; another
   // geometry re-records.  Invalidated with hist (same derivation chain).
+  // The plan's payload is tile-major: tile t's bucket-sorted staging lies at
+  // [t * TILE, (t + 1) * TILE) of the value buffer and of plan_rk, and P2
+  // fetches a bucket's run out of each tile through plan_runs.
   void*   d_plan_dst = nullptr;  // u16[n]: row -> slot in its tile's bucket-
                                  // sorted LDS staging; 0xFFFF = key out of range
-  void*   d_plan_rk = nullptr;   // u16[radix_rows]: low-key stream P2 reads
-  void*   d_plan_tab = nullptr;  // u32[ntiles][2*nb+1]: tile bucket offsets
-                                 // (nb+1, last = staged rows) + region bases
-  void*   d_plan_meta = nullptr; // u64[2]: region slot of the odd tail row
-                                 // (~0 = none), out-of-range rows recorded
+  void*   d_plan_rk = nullptr;   // u16[ntiles * TILE]: low key of staged slot p
+                                 // of tile t at [t * TILE + p]
+  void*   d_plan_runs = nullptr; // u32[nb][ntiles], bucket-major: the bucket's
+                                 // run in the tile, start | length << 16
+  void*   d_plan_items = nullptr;  // GbTileItem[plan_items_n]: P2 work items,
+                                   // a bucket's items contiguous, in tile order
+  void*   d_plan_item0 = nullptr;  // u32[nb + 1]: bucket -> its first item
+  void*   d_plan_order = nullptr;  // u32[plan_items_n]: P2 block -> item,
+                                   // costliest item first
+  void*   d_plan_meta = nullptr; // u64: out-of-range rows recorded
+  int64_t plan_items_n = 0;
   int64_t plan_kmin = 0;
   int64_t plan_nslots = 0;
   int     plan_rl = 0;           // 0 = no plan
@@ -423,8 +432,12 @@ using PlanOwner = std::unique_ptr<hf_filterplan, int (*)(hf_filterplan*)>;
 void GbKeyCache::drop_plan() {
   drop_dev(d_plan_dst);
   drop_dev(d_plan_rk);
-  drop_dev(d_plan_tab);
+  drop_dev(d_plan_runs);
+  drop_dev(d_plan_items);
+  drop_dev(d_plan_item0);
+  drop_dev(d_plan_order);
   drop_dev(d_plan_meta);
+  plan_items_n = 0;
   plan_rl = 0;
   drop_dev(d_gidx);
   drop_dev(d_gkeys);
@@ -868,7 +881,11 @@ __global__ void __launch_bounds__(BLOCK) k_gb_accum(
 //                        a plan on the key column and later calls run
 //      k_gb_replay     : the recorded value permutation — read 2 B dst +
 //                        8 B val, write 8 B val per row; no key reads, no
-//                        atomics (P2 reads the low keys from the plan)
+//                        atomics (P2 reads the low keys from the plan).  The
+//                        plan's payload is tile-major: record and replay
+//                        write each tile's bucket-sorted staging verbatim
+//                        as whole lines, and P2 fetches a bucket's run out
+//                        of each tile (TILED)
 //   P2 k_gb_bucket_agg : stream each bucket chunk into an LDS table
 //                        (ds_add_f64 behind a register run-accumulator for
 //                        skewed keys), merge non-empty slots into the
@@ -934,8 +951,17 @@ __global__ void __launch_bounds__(BLOCK) k_conv_keys32(
 
 struct GbPlanRec {
   unsigned short* dst;
-  unsigned* tab;
-  unsigned long long* meta;
+  unsigned* runs;            // [nb][ntiles]
+  unsigned long long* meta;  // out-of-range rows
+};
+
+// P2 work item on a plan: the runs of one bucket in tiles [tile_begin,
+// tile_end), at most AGG_CHUNK rows.
+struct GbTileItem {
+  int32_t bucket;
+  int32_t tile_begin;
+  int32_t tile_end;
+  uint32_t row0;  // rows of the bucket before tile_begin
 };
 
 // P1: LDS-staged bucket-sorted tiles.  Row pairs load 16 B-vectorized
@@ -950,11 +976,15 @@ struct GbPlanRec {
 // that point — so their ~700-cycle latency hides under t's writeout + barrier
 // instead of serializing at the top of the next iteration (the 81%
 // wave-parked stall of the round-1 kernel, profiles/r01b/sq_scatter.txt).
-// REC: the plan-recording variant (first radix call on a key column).  Same
-// work, plus it keeps what a replay needs: each row's staging slot (`dst`,
-// one coalesced ushort2 per row pair), the tile's offset/base table row, the
-// tail row's region slot and the out-of-range count.  It reads the int64
-// keys; the plan-less variant (!REC) reads the cached u32 copy.
+// REC: the plan-recording variant (first radix call on a key column).  It
+// ranks and stages the same way but does not partition across tiles: the
+// tile's bucket-sorted staging goes out verbatim at tile * TILE (values to
+// r0, low keys to rk), so it takes no global cursor, and the odd last row is
+// one more row of the last tile.  It keeps what a replay and P2 need: each
+// row's staging slot (`dst`, one coalesced ushort2 per row pair), the tile's
+// run of every bucket (`runs`, bucket-major) and the out-of-range count.  It
+// reads the int64 keys; the plan-less variant (!REC) reads the cached u32
+// copy.
 template <int NV, int RPT, int BLK, int RL, bool REC>
 __global__ void __launch_bounds__(BLK) k_gb_scatter(
     const int64_t* __restrict__ keys, const unsigned* __restrict__ keys32,
@@ -969,22 +999,22 @@ __global__ void __launch_bounds__(BLK) k_gb_scatter(
   constexpr int TILE = BLK * RPT;
   constexpr int PAIRS = RPT / 2;
   static_assert(!REC || TILE < 0xFFFF, "plan dst is u16 with 0xFFFF reserved");
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (!REC && (n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
     // odd tail row: direct single-row reservation + write
-    const int64_t k = K32 ? (int64_t)keys32[n - 1] : keys[n - 1] - key_min;
+    const int64_t k = (int64_t)keys32[n - 1];
     if ((uint64_t)k < (uint64_t)n_slots) {
       const int b = (int)(k >> RL);
       const int64_t pos = (int64_t)atomicAdd(&cursors[b], 1u);
       rk[pos] = (unsigned short)(k & ((1 << RL) - 1));
       if (NV > 0) r0[pos] = v0[n - 1];
       if (NV > 1) r1[pos] = v1[n - 1];
-      if (REC) rec.meta[0] = (unsigned long long)pos;
     } else {
       atomicAdd(err, 1ULL);
-      if (REC) atomicAdd(&rec.meta[1], 1ULL);
     }
   }
   const int64_t npair_total = n >> 1;
+  // REC: the odd last row is the x half of pair npair_total
+  const int64_t half_pair = (REC && (n & 1)) ? npair_total : -1;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   double* sval0 = reinterpret_cast<double*>(smem_raw);            // [TILE]
   double* sval1 = sval0 + (NV > 1 ? TILE : 0);
@@ -996,7 +1026,7 @@ __global__ void __launch_bounds__(BLK) k_gb_scatter(
   unsigned* s_total = it_gbase + nb;  // scalar; keep ALL LDS in the dynamic
                                       // region (a static __shared__ would
                                       // shift the base off 16B — G17)
-  const int64_t ntiles = (npair_total * 2 + TILE - 1) / TILE;
+  const int64_t ntiles = ((REC ? n : npair_total * 2) + TILE - 1) / TILE;
 
   // only the K32-selected key array and the first NV value arrays are ever
   // touched; the others constant-fold away (template params) and cost no
@@ -1016,6 +1046,9 @@ __global__ void __launch_bounds__(BLK) k_gb_scatter(
           kraw64[j] = reinterpret_cast<const longlong2*>(keys)[pj];
         if (NV > 0) vraw0[j] = reinterpret_cast<const double2*>(v0)[pj];
         if (NV > 1) vraw1[j] = reinterpret_cast<const double2*>(v1)[pj];
+      } else if (REC && pj == half_pair) {
+        kraw64[j].x = keys[n - 1];
+        if (NV > 0) vraw0[j].x = v0[n - 1];
       }
     }
   };
@@ -1041,14 +1074,23 @@ __global__ void __launch_bounds__(BLK) k_gb_scatter(
           lk[a] = (unsigned)(ka & ((1 << RL) - 1));
         } else {
           atomicAdd(err, 1ULL);
-          if (REC) atomicAdd(&rec.meta[1], 1ULL);
+          if (REC) atomicAdd(rec.meta, 1ULL);
         }
         if ((uint64_t)kb < (uint64_t)n_slots) {
           lb[bslot] = (int)(kb >> RL);
           lk[bslot] = (unsigned)(kb & ((1 << RL) - 1));
         } else {
           atomicAdd(err, 1ULL);
-          if (REC) atomicAdd(&rec.meta[1], 1ULL);
+          if (REC) atomicAdd(rec.meta, 1ULL);
+        }
+      } else if (REC && pj == half_pair) {
+        const int64_t ka = kraw64[j].x - key_min;
+        if ((uint64_t)ka < (uint64_t)n_slots) {
+          lb[a] = (int)(ka >> RL);
+          lk[a] = (unsigned)(ka & ((1 << RL) - 1));
+        } else {
+          atomicAdd(err, 1ULL);
+          atomicAdd(rec.meta, 1ULL);
         }
       }
     }
@@ -1075,9 +1117,11 @@ __global__ void __launch_bounds__(BLK) k_gb_scatter(
       if (lane == 0) *s_total = carry;
     }
     __syncthreads();
-    for (int t = threadIdx.x; t < nb; t += blockDim.x) {
-      const unsigned c = it_cnt[t];
-      if (c) it_gbase[t] = atomicAdd(&cursors[t], c);
+    if (!REC) {
+      for (int t = threadIdx.x; t < nb; t += blockDim.x) {
+        const unsigned c = it_cnt[t];
+        if (c) it_gbase[t] = atomicAdd(&cursors[t], c);
+      }
     }
 #pragma unroll
     for (int j = 0; j < RPT; ++j) {
@@ -1092,27 +1136,24 @@ __global__ void __launch_bounds__(BLK) k_gb_scatter(
 #pragma unroll
       for (int j = 0; j < PAIRS; ++j) {
         const int64_t pj = tile * (TILE / 2) + (int64_t)j * BLK + threadIdx.x;
+        const int a = 2 * j, bslot = 2 * j + 1;
         if (pj < npair_total) {
-          const int a = 2 * j, bslot = 2 * j + 1;
           ushort2 d;
           d.x = lb[a] >= 0 ? (unsigned short)(it_off[lb[a]] + lr[a]) : 0xFFFF;
           d.y = lb[bslot] >= 0
                     ? (unsigned short)(it_off[lb[bslot]] + lr[bslot])
                     : 0xFFFF;
           reinterpret_cast<ushort2*>(rec.dst)[pj] = d;
+        } else if (pj == half_pair) {
+          rec.dst[n - 1] =
+              lb[a] >= 0 ? (unsigned short)(it_off[lb[a]] + lr[a]) : 0xFFFF;
         }
       }
+      // the tile's run of every bucket (before the loop-bottom clear of it_cnt)
+      for (int t = threadIdx.x; t < nb; t += blockDim.x)
+        rec.runs[(int64_t)t * ntiles + tile] = it_off[t] | (it_cnt[t] << 16);
     }
-    __syncthreads();  // staging visible; it_cnt reads (scan) long done
-    if (REC) {
-      // the tile's table row (it_gbase of an empty bucket is never read)
-      unsigned* row = rec.tab + tile * (2 * (int64_t)nb + 1);
-      for (int t = threadIdx.x; t < nb; t += blockDim.x) {
-        row[t] = it_off[t];
-        row[nb + 1 + t] = it_cnt[t] ? it_gbase[t] : 0u;
-      }
-      if (threadIdx.x == 0) row[nb] = *s_total;
-    }
+    __syncthreads();  // staging visible; it_cnt reads (scan, runs) done
     // registers are dead — issue the NEXT tile's loads so they fly during
     // this tile's writeout, and clear it_cnt for the next rank phase
     const int64_t nxt = tile + gridDim.x;
@@ -1121,7 +1162,8 @@ __global__ void __launch_bounds__(BLK) k_gb_scatter(
     const int staged = (int)*s_total;
     for (int p = threadIdx.x; p < staged; p += blockDim.x) {
       const unsigned b = skey[p] >> 16;
-      const int64_t pos = (int64_t)it_gbase[b] + (p - it_off[b]);
+      const int64_t pos = REC ? tile * (int64_t)TILE + p
+                              : (int64_t)it_gbase[b] + (p - it_off[b]);
       rk[pos] = (unsigned short)(skey[p] & 0xFFFF);
       if (NV > 0) r0[pos] = sval0[p];
       if (NV > 1) r1[pos] = sval1[p];
@@ -1136,47 +1178,40 @@ __global__ void __launch_bounds__(BLK) k_gb_scatter(
 constexpr int GB_PLAN_BLK = 1024;
 constexpr int GB_PLAN_RPT = 12;
 constexpr int GB_PLAN_TILE = GB_PLAN_BLK * GB_PLAN_RPT;
+// replay writeout flavour when HF_GB_NT_STORE is unset (profiles/r11)
+constexpr bool GB_REPLAY_NT_DEFAULT = true;
 
 // P1 steady state: replay a recorded plan as a pure value permutation, one
 // value column per launch.  Reads 2 B dst + 8 B value per row, writes 8 B;
-// no key reads, no LDS atomics, no scan, no global atomics.  Same software
-// pipelining as k_gb_scatter: the next tile's loads (dst, values and table
-// row) are issued right after this tile's staging.
-// The writeout recovers the bucket b of a staged slot p from the tile's
-// offsets alone: b = the last bucket with it_off[b] <= p, found by a
-// fixed-trip binary search per slot.  The RPT searches of a thread are
-// independent and unrolled side by side, so their LDS reads overlap; work
-// is split by slot, never by bucket, so a zipf head bucket that fills most
-// of a tile costs nothing extra.
-template <int RPT, int BLK>
+// no key reads, no LDS atomics, no scan, no global atomics, no table.  A
+// tile's staging goes out verbatim at tile * TILE, as whole aligned 16-byte
+// stores per lane; slots past the tile's staged count (a tile with
+// out-of-range keys, the end of the last tile) carry stale LDS and are never
+// read by P2, which follows the recorded runs.  Same software pipelining as
+// k_gb_scatter: the next tile's loads are issued right after this tile's
+// staging.  NT: non-temporal stores for the writeout.
+template <int RPT, int BLK, bool NT>
 __global__ void __launch_bounds__(BLK) k_gb_replay(
     const unsigned short* __restrict__ dst, const double* __restrict__ v,
-    int64_t n, int nb, int search0, const unsigned* __restrict__ tab,
-    const unsigned long long* __restrict__ meta, double* __restrict__ r0,
-    unsigned long long* __restrict__ err, int add_err) {
+    int64_t n, const unsigned long long* __restrict__ meta,
+    double* __restrict__ r0, unsigned long long* __restrict__ err,
+    int add_err) {
   constexpr int TILE = BLK * RPT;
   constexpr int PAIRS = RPT / 2;
-  constexpr int TABR = 3;  // table row is 2*nb+1 <= 2049 words <= 3 per thread
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    if (n & 1) {
-      const unsigned long long pos = meta[0];
-      if (pos != ~0ULL) r0[pos] = v[n - 1];
-    }
+  typedef double nd2 __attribute__((ext_vector_type(2)));
+  if (add_err && blockIdx.x == 0 && threadIdx.x == 0) {
     // out-of-range keys were counted while recording; every call reports them
-    const unsigned long long oor = meta[1];
-    if (add_err && oor) atomicAdd(err, oor);
+    const unsigned long long oor = meta[0];
+    if (oor) atomicAdd(err, oor);
   }
   const int64_t npair_total = n >> 1;
-  const int64_t ntiles = (npair_total * 2 + TILE - 1) / TILE;
-  const int tabw = 2 * nb + 1;
+  const int64_t half_pair = (n & 1) ? npair_total : -1;  // the odd last row
+  const int64_t ntiles = (n + TILE - 1) / TILE;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   double* sval = reinterpret_cast<double*>(smem_raw);         // [TILE]
-  unsigned* it_off = reinterpret_cast<unsigned*>(sval + TILE);  // [nb + 1]
-  const unsigned* it_gbase = it_off + nb + 1;                   // [nb]
 
   unsigned draw[PAIRS];
   double2 vraw[PAIRS];
-  unsigned traw[TABR];
   auto issue_loads = [&](int64_t tile) {
 #pragma unroll
     for (int j = 0; j < PAIRS; ++j) {
@@ -1184,56 +1219,139 @@ __global__ void __launch_bounds__(BLK) k_gb_replay(
       if (pj < npair_total) {
         draw[j] = reinterpret_cast<const unsigned*>(dst)[pj];
         vraw[j] = reinterpret_cast<const double2*>(v)[pj];
+      } else if (pj == half_pair) {
+        draw[j] = dst[n - 1] | 0xFFFF0000u;
+        vraw[j].x = v[n - 1];
       }
-    }
-    const unsigned* row = tab + tile * (int64_t)tabw;
-#pragma unroll
-    for (int j = 0; j < TABR; ++j) {
-      const int t = j * BLK + threadIdx.x;
-      if (t < tabw) traw[j] = row[t];
     }
   };
 
   int64_t tile = blockIdx.x;
   if (tile < ntiles) issue_loads(tile);
   for (; tile < ntiles; tile += gridDim.x) {
-    __syncthreads();  // previous tile's writeout is done with sval / table
+    __syncthreads();  // previous tile's writeout is done with sval
 #pragma unroll
     for (int j = 0; j < PAIRS; ++j) {
       const int64_t pj = tile * (TILE / 2) + (int64_t)j * BLK + threadIdx.x;
-      if (pj < npair_total) {
+      if (pj < npair_total || pj == half_pair) {
         const unsigned pa = draw[j] & 0xFFFFu, pb = draw[j] >> 16;
         if (pa < (unsigned)TILE) sval[pa] = vraw[j].x;
         if (pb < (unsigned)TILE) sval[pb] = vraw[j].y;
       }
     }
-#pragma unroll
-    for (int j = 0; j < TABR; ++j) {
-      const int t = j * BLK + threadIdx.x;
-      if (t < tabw) it_off[t] = traw[j];
-    }
-    __syncthreads();  // staging + table visible
+    __syncthreads();  // staging visible
     const int64_t nxt = tile + gridDim.x;
     if (nxt < ntiles) issue_loads(nxt);
-    const int staged = (int)it_off[nb];
-    int b[RPT];
+    // rows of this tile, rounded up to a pair (r0 holds ntiles * TILE rows)
+    const int64_t left = n - tile * (int64_t)TILE;
+    const int pairs = left >= TILE ? TILE / 2 : (int)((left + 1) >> 1);
+    nd2* out = reinterpret_cast<nd2*>(r0 + tile * (int64_t)TILE);
+    const nd2* in = reinterpret_cast<const nd2*>(sval);
 #pragma unroll
-    for (int j = 0; j < RPT; ++j) b[j] = 0;
-    // it_off[0] == 0 <= p, and it_off[nb] == staged > p bounds the answer
-    for (int s = search0; s > 0; s >>= 1) {
-#pragma unroll
-      for (int j = 0; j < RPT; ++j) {
-        const int p = j * BLK + threadIdx.x;
-        const int m = b[j] + s;
-        if (p < staged && m < nb && it_off[m] <= (unsigned)p) b[j] = m;
+    for (int j = 0; j < PAIRS; ++j) {
+      const int q = j * BLK + threadIdx.x;
+      if (q < pairs) {
+        if (NT)
+          __builtin_nontemporal_store(in[q], out + q);
+        else
+          out[q] = in[q];
       }
     }
+  }
+}
+
+// The P2 work items of a freshly recorded plan, from the per-(bucket, tile)
+// run lengths; one wave per bucket.  Tile t of a bucket belongs to item
+// (cost of the bucket before t) / cut, where a tile costs its rows of the
+// bucket, but GB_TILE_COST at the least: the items are row-balanced where the
+// runs are long, and where a bucket has a few rows in each of very many tiles
+// (a zipf tail) an item is bounded in tiles, since such an item is bound by
+// its chain of round trips, not by its rows.  A tile costs less than the cut,
+// so the
+// item index grows by at most one per tile, and an item holds fewer
+// than cut + TILE <= AGG_CHUNK rows.
+// Two passes of the same walk: FILL = false counts the bucket's items into
+// nitems[b]; FILL = true writes them and item0.
+// The cut (gb_item_cut) aims at GB_ITEMS_MIN items or more: a frame of 1e8
+// rows in 62 buckets would otherwise keep 62 of 256 CUs busy, and P2 on a
+// plan is bound by what one CU gathers (profiles/r11).  Not below 2^18 rows,
+// so that the table an item flushes or merges stays small beside its rows.
+constexpr int64_t GB_ITEM_CUT_MAX = AGG_CHUNK - GB_PLAN_TILE;
+constexpr int64_t GB_ITEM_CUT_MIN = 1 << 18;
+constexpr int64_t GB_ITEMS_MIN = 256;
+constexpr int64_t GB_TILE_COST = 128;  // rows a tile of an item counts for
+
+template <bool FILL>
+__global__ void __launch_bounds__(64) k_gb_plan_items(
+    const unsigned* __restrict__ runs, int64_t ntiles, int nb, int64_t cut,
+    unsigned* __restrict__ nitems, unsigned* __restrict__ item0,
+    GbTileItem* __restrict__ items) {
+  const int b = blockIdx.x;
+  const int lane = threadIdx.x;
+  const unsigned* row = runs + (int64_t)b * ntiles;
+  unsigned first = 0, mine = 0;
+  if (FILL) {
+    // this bucket's first item: the items of the buckets before it
+    unsigned acc = 0;
+    for (int t = lane; t < nb; t += 64) acc += t < b ? nitems[t] : 0u;
 #pragma unroll
-    for (int j = 0; j < RPT; ++j) {
-      const int p = j * BLK + threadIdx.x;
-      if (p < staged)
-        r0[(int64_t)it_gbase[b[j]] + ((unsigned)p - it_off[b[j]])] = sval[p];
+    for (int d = 32; d > 0; d >>= 1) acc += __shfl_xor(acc, d);
+    first = acc;
+    mine = nitems[b];
+    if (lane == 0) {
+      item0[b] = first;
+      if (b == nb - 1) item0[nb] = first + mine;
     }
+    if (mine == 0) return;
+  }
+  int64_t carry = 0;      // rows of the bucket before this stride of tiles
+  int64_t ccarry = 0;     // their cost
+  int64_t last_excl = -1; // cost before the last non-empty tile
+  int prev_item = -1;     // item of the tile before this stride
+  for (int64_t t0 = 0; t0 < ntiles; t0 += 64) {
+    const int64_t t = t0 + lane;
+    const unsigned len = t < ntiles ? row[t] >> 16 : 0u;
+    const unsigned cost =
+        t < ntiles ? max(len, (unsigned)GB_TILE_COST) : 0u;
+    unsigned incl = len, cincl = cost;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const unsigned up = __shfl_up(incl, d);
+      const unsigned cup = __shfl_up(cincl, d);
+      if (lane >= d) incl += up;
+      if (lane >= d) cincl += cup;
+    }
+    const int64_t excl = carry + incl - len;      // rows before t
+    const int64_t cexcl = ccarry + cincl - cost;  // cost before t
+    if (!FILL) {
+      int64_t e = len ? cexcl : -1;
+#pragma unroll
+      for (int d = 32; d > 0; d >>= 1) {
+        const int64_t o = __shfl_xor(e, d);
+        e = o > e ? o : e;
+      }
+      if (e > last_excl) last_excl = e;
+    } else {
+      // trailing empty tiles stay in the last item
+      const int it = (int)min((int64_t)(cexcl / cut), (int64_t)mine - 1);
+      int before = __shfl_up(it, 1);
+      if (lane == 0) before = prev_item;
+      if (t < ntiles && it != before) {
+        items[first + it].bucket = b;
+        items[first + it].tile_begin = (int)t;
+        items[first + it].row0 = (unsigned)excl;
+        if (it > 0) items[first + it - 1].tile_end = (int)t;
+      }
+      prev_item = __shfl(it, 63);
+    }
+    carry += __shfl(incl, 63);
+    ccarry += __shfl(cincl, 63);
+  }
+  if (!FILL) {
+    if (lane == 0)
+      nitems[b] = last_excl < 0 ? 0u : (unsigned)(last_excl / cut) + 1u;
+  } else if (lane == 0) {
+    items[first + mine - 1].tile_end = (int)ntiles;
   }
 }
 
@@ -1241,7 +1359,7 @@ __global__ void __launch_bounds__(BLK) k_gb_replay(
 // out-of-range count to the shared error word so compaction still raises.
 __global__ void k_gb_plan_err(const unsigned long long* __restrict__ meta,
                               unsigned long long* __restrict__ err) {
-  if (blockIdx.x == 0 && threadIdx.x == 0 && meta[1]) atomicAdd(err, meta[1]);
+  if (blockIdx.x == 0 && threadIdx.x == 0 && meta[0]) atomicAdd(err, meta[0]);
 }
 
 // P2: one work item per (bucket, chunk), one block per item; one value
@@ -1257,23 +1375,45 @@ __global__ void k_gb_plan_err(const unsigned long long* __restrict__ meta,
 // from the first row; only the last chunk of a bucket can have an odd tail.
 // PART (hf_groupby_reduce on a cached group map): presence is already known,
 // so no touch bytes and no ROWCNT, and instead of the atomic merge the block
-// stores its whole table — identity in untouched slots — as row blockIdx.x of
+// stores its whole table — identity in untouched slots — as its item's row of
 // part_sums / part_cnt with plain 16-byte stores; k_gb_combine folds the rows
 // of a bucket.
 // A 16384-slot table (RL = 14, sums without counts) is 128 KB, so one block
 // fits a CU: it runs 1024 threads, the same 16 waves per CU as two 512-thread
 // blocks at RL = 13.  The loops stride by blockDim.x.
+// Two row iterations feed the same accumulate / flush code:
+//  * !TILED, the plan-less path: the item is a contiguous chunk of a bucket
+//    region (GbWorkItem), streamed as row pairs;
+//  * TILED, on a plan: the item is the bucket's runs in a range of tiles
+//    (GbTileItem) of the tile-major payload.  Each wave takes chunks of up to
+//    64 consecutive tiles: one coalesced load brings the chunk's run
+//    descriptors, one per lane (the next chunk's are fetched before this
+//    chunk's rows), and a wave scan turns the lengths into row offsets.  Then
+//    either the wave sweeps the chunk's rows as one flat stream, 64 rows per
+//    step and GB_P2_TU steps in flight, each lane keeping a cursor into the
+//    chunk's offsets in LDS that only ever moves forward (about one 8-byte LDS
+//    read per run a lane enters — no per-row search); or, when no run of the
+//    chunk is longer than GB_P2_SPARSE rows (a zipf tail bucket), every lane
+//    reads its own run, so 64 runs share one round trip.  Rows are loaded one
+//    per lane (8 B + 2 B): runs start at any row, so there are no pair loads
+//    and no pad rows.  No barrier inside the walk: the waves run apart until
+//    the flush.
 constexpr int gb_p2_block(int rl) { return rl >= 14 ? 1024 : 512; }
+constexpr int GB_P2_TU = 8;       // 64-row steps in flight per wave (TILED)
+constexpr int GB_P2_SPARSE = 8;   // longest run of a lane-per-run chunk
 
 template <bool ROWCNT, bool CNT, bool HAVE_VAL, int RL, int AOP,
-          bool PART = false>
+          bool PART = false, bool TILED = false>
 __global__ void __launch_bounds__(gb_p2_block(RL)) k_gb_bucket_agg(
     const double* __restrict__ vals, const unsigned short* __restrict__ lowkeys,
-    const GbWorkItem* __restrict__ work, int64_t n_slots,
+    const void* __restrict__ work, int64_t n_slots,
     double* __restrict__ gsums, unsigned long long* __restrict__ growcnt,
     unsigned long long* __restrict__ gcounts,
     double* __restrict__ part_sums = nullptr,   // [gridDim.x][RANGE] (PART)
-    unsigned* __restrict__ part_cnt = nullptr) {  // likewise, with CNT
+    unsigned* __restrict__ part_cnt = nullptr,  // likewise, with CNT
+    const unsigned* __restrict__ runs = nullptr,  // [nb][ntiles] (TILED)
+    int64_t ntiles = 0,
+    const unsigned* __restrict__ order = nullptr) {  // block -> item (TILED)
   static_assert(!PART || (HAVE_VAL && !ROWCNT), "PART flushes value tables");
   static_assert(RL <= 16, "low keys are u16");
   static_assert(RL <= 13 || !CNT, "no LDS for a counts table beside 16384 sums");
@@ -1281,29 +1421,19 @@ __global__ void __launch_bounds__(gb_p2_block(RL)) k_gb_bucket_agg(
   __shared__ __attribute__((aligned(16))) double lsums[HAVE_VAL ? RANGE : 1];
   __shared__ __attribute__((aligned(16))) unsigned lcnt[CNT ? RANGE : 1];
   __shared__ unsigned char ltouch[PART ? 1 : RANGE];
-  const GbWorkItem w = work[blockIdx.x];
+  // TILED: per wave, a chunk's {end row, payload offset - start row} per run
+  __shared__ uint2 lruns[TILED ? gb_p2_block(RL) : 1];
+  // TILED: the blocks take the items in the plan's dispatch order
+  const unsigned item = TILED ? order[blockIdx.x] : blockIdx.x;
+  const int bucket = TILED
+      ? reinterpret_cast<const GbTileItem*>(work)[item].bucket
+      : reinterpret_cast<const GbWorkItem*>(work)[item].bucket;
   for (int s = threadIdx.x; s < RANGE; s += blockDim.x) {
     if (HAVE_VAL) lsums[s] = agg_identity<AOP>();
     if (!PART) ltouch[s] = 0;
     if (CNT) lcnt[s] = 0;
   }
   __syncthreads();
-  const int64_t end = w.start + w.len;
-  auto one_row = [&](int64_t i) {
-    const int slot = lowkeys[i];
-    if (!PART) ltouch[slot] = 1;
-    if (HAVE_VAL) {
-      const double v = vals[i];
-      if (v == v) {
-        lds_slot_agg<AOP>(&lsums[slot], v);
-        if (CNT) atomicAdd(&lcnt[slot], 1u);
-      }
-    }
-  };
-  const int64_t a0 = w.start;  // even (see above)
-  const int64_t npair = (end - a0) >> 1;
-  const ushort2* k2 = reinterpret_cast<const ushort2*>(lowkeys + a0);
-  const double2* v2 = reinterpret_cast<const double2*>(vals + a0);
   // register run-accumulation: consecutive rows of a lane's stream that
   // share a slot combine in a register before ONE LDS op — on skewed
   // keys the head slot dominates its bucket and the per-slot ds_add
@@ -1335,72 +1465,173 @@ __global__ void __launch_bounds__(gb_p2_block(RL)) k_gb_bucket_agg(
       }
     }
   };
-  // both streams are read once: non-temporal loads (the builtin takes native
-  // scalars and vectors, hence the u32 / ext_vector views of a pair);
-  // P2 1.70 -> 1.56 ms on top of the two-pair loop (profiles/r08)
-  auto ld_k = [&](int64_t i) {
-    const unsigned r = __builtin_nontemporal_load(
-        reinterpret_cast<const unsigned*>(k2) + i);
-    return make_ushort2((unsigned short)(r & 0xFFFFu),
-                        (unsigned short)(r >> 16));
-  };
-  auto ld_v = [&](int64_t i) {
-    typedef double nd2 __attribute__((ext_vector_type(2)));
-    const nd2 r = __builtin_nontemporal_load(
-        reinterpret_cast<const nd2*>(v2) + i);
-    return make_double2(r.x, r.y);
-  };
-  auto feed_pair = [&](ushort2 kk, double2 vv) {
-    if (HAVE_VAL) {
-      feed(kk.x, vv.x);
-      feed(kk.y, vv.y);
-    } else {
-      ltouch[kk.x] = 1;
-      ltouch[kk.y] = 1;
-    }
-  };
-  // GB_P2_U pairs in flight per lane: a body trip issues the loads of U
-  // block-strides, then feeds them in stride order, so a lane sees the rows
-  // it would see one stride at a time, in that order.  The trip condition is
-  // block-uniform; the last < U * blockDim.x pairs go one stride at a time.
-  constexpr int U = GB_P2_U;
-  const int64_t bstep = (int64_t)U * blockDim.x;
-  int64_t base = 0;
-  for (; base + bstep <= npair; base += bstep) {
-    ushort2 kk[U];
-    double2 vv[U];
+  if constexpr (!TILED) {
+    const GbWorkItem w =
+        reinterpret_cast<const GbWorkItem*>(work)[blockIdx.x];
+    const int64_t end = w.start + w.len;
+    const int64_t a0 = w.start;  // even (see above)
+    const int64_t npair = (end - a0) >> 1;
+    const ushort2* k2 = reinterpret_cast<const ushort2*>(lowkeys + a0);
+    const double2* v2 = reinterpret_cast<const double2*>(vals + a0);
+    // both streams are read once: non-temporal loads (the builtin takes
+    // native scalars and vectors, hence the u32 / ext_vector views of a
+    // pair); P2 1.70 -> 1.56 ms on top of the two-pair loop (profiles/r08)
+    auto ld_k = [&](int64_t i) {
+      const unsigned r = __builtin_nontemporal_load(
+          reinterpret_cast<const unsigned*>(k2) + i);
+      return make_ushort2((unsigned short)(r & 0xFFFFu),
+                          (unsigned short)(r >> 16));
+    };
+    auto ld_v = [&](int64_t i) {
+      typedef double nd2 __attribute__((ext_vector_type(2)));
+      const nd2 r = __builtin_nontemporal_load(
+          reinterpret_cast<const nd2*>(v2) + i);
+      return make_double2(r.x, r.y);
+    };
+    auto feed_pair = [&](ushort2 kk, double2 vv) {
+      if (HAVE_VAL) {
+        feed(kk.x, vv.x);
+        feed(kk.y, vv.y);
+      } else {
+        ltouch[kk.x] = 1;
+        ltouch[kk.y] = 1;
+      }
+    };
+    // GB_P2_U pairs in flight per lane: a body trip issues the loads of U
+    // block-strides, then feeds them in stride order, so a lane sees the rows
+    // it would see one stride at a time, in that order.  The trip condition
+    // is block-uniform; the last < U * blockDim.x pairs go one stride at a
+    // time.
+    constexpr int U = GB_P2_U;
+    const int64_t bstep = (int64_t)U * blockDim.x;
+    int64_t base = 0;
+    for (; base + bstep <= npair; base += bstep) {
+      ushort2 kk[U];
+      double2 vv[U];
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int64_t i = base + (int64_t)u * blockDim.x + threadIdx.x;
-      kk[u] = ld_k(i);
-      if (HAVE_VAL) vv[u] = ld_v(i);
-    }
+      for (int u = 0; u < U; ++u) {
+        const int64_t i = base + (int64_t)u * blockDim.x + threadIdx.x;
+        kk[u] = ld_k(i);
+        if (HAVE_VAL) vv[u] = ld_v(i);
+      }
 #pragma unroll
-    for (int u = 0; u < U; ++u) feed_pair(kk[u], vv[u]);
-  }
-  for (int64_t i = base + threadIdx.x; i < npair; i += blockDim.x) {
-    const ushort2 kk = ld_k(i);
-    double2 vv = make_double2(0.0, 0.0);
-    if (HAVE_VAL) vv = ld_v(i);
-    feed_pair(kk, vv);
+      for (int u = 0; u < U; ++u) feed_pair(kk[u], vv[u]);
+    }
+    for (int64_t i = base + threadIdx.x; i < npair; i += blockDim.x) {
+      const ushort2 kk = ld_k(i);
+      double2 vv = make_double2(0.0, 0.0);
+      if (HAVE_VAL) vv = ld_v(i);
+      feed_pair(kk, vv);
+    }
+    flush();
+    if (((end - a0) & 1) && threadIdx.x == 0) {
+      const int slot = lowkeys[end - 1];
+      if (!PART) ltouch[slot] = 1;
+      if (HAVE_VAL) {
+        const double v = vals[end - 1];
+        if (v == v) {
+          lds_slot_agg<AOP>(&lsums[slot], v);
+          if (CNT) atomicAdd(&lcnt[slot], 1u);
+        }
+      }
+    }
+  } else {
+    constexpr int TILE = GB_PLAN_TILE;
+    constexpr int U = GB_P2_TU;
+    const GbTileItem w = reinterpret_cast<const GbTileItem*>(work)[item];
+    const int lane = threadIdx.x & 63;
+    const int nw = blockDim.x >> 6;
+    // tiles per chunk: every wave gets the same number of chunks, of at most
+    // 64 tiles and of equal size (a block is as slow as its slowest wave; an
+    // item of few tiles — sorted keys — still gives every wave a share)
+    const int nt = w.tile_end - w.tile_begin;
+    const int per_wave = (nt + nw * 64 - 1) / (nw * 64);  // chunks per wave
+    const int cs = (nt + nw * per_wave - 1) / (nw * per_wave);
+    const int64_t cstep = (int64_t)nw * cs;
+    const unsigned* row = runs + (int64_t)w.bucket * ntiles;
+    uint2* we = lruns + (threadIdx.x & ~63);
+    auto ld_desc = [&](int64_t c) {
+      const int64_t t = c + lane;
+      return (lane < cs && t < w.tile_end) ? row[t] : 0u;
+    };
+    auto row_in = [&](const unsigned short* kb, const double* vb, unsigned at,
+                      unsigned& k, double& v) {
+      k = __builtin_nontemporal_load(kb + at);
+      if (HAVE_VAL) v = __builtin_nontemporal_load(vb + at);
+    };
+    int64_t c = w.tile_begin + (int64_t)(threadIdx.x >> 6) * cs;
+    unsigned d = c < w.tile_end ? ld_desc(c) : 0u;
+    for (; c < w.tile_end; c += cstep) {  // wave-uniform trips
+      const unsigned len = d >> 16, st = d & 0xFFFFu;
+      d = c + cstep < w.tile_end ? ld_desc(c + cstep) : 0u;
+      unsigned incl = len, longest = len;
+#pragma unroll
+      for (int s = 1; s < 64; s <<= 1) {
+        const unsigned up = __shfl_up(incl, s);
+        if (lane >= s) incl += up;
+        longest = max(longest, (unsigned)__shfl_xor(longest, s));
+      }
+      const unsigned total = __shfl(incl, 63);
+      const unsigned short* kb = lowkeys + c * TILE;
+      const double* vb = vals + c * TILE;
+      if (longest <= (unsigned)GB_P2_SPARSE) {
+        // a lane per run
+        const unsigned at = (unsigned)lane * TILE + st;
+        for (unsigned k0 = 0; k0 < longest; k0 += U) {
+          unsigned kk[U];
+          double vv[U];
+#pragma unroll
+          for (int u = 0; u < U; ++u) {
+            vv[u] = 0.0;
+            if (k0 + u < len) row_in(kb, vb, at + k0 + u, kk[u], vv[u]);
+          }
+#pragma unroll
+          for (int u = 0; u < U; ++u)
+            if (k0 + u < len) feed(kk[u], vv[u]);
+        }
+      } else {
+        // the chunk's rows as one stream; run j ends at row we[j].x and its
+        // row r lies at payload offset we[j].y + r (mod 2^32)
+        we[lane] = make_uint2(incl, (unsigned)lane * TILE + st - (incl - len));
+        __builtin_amdgcn_wave_barrier();
+        int j = 0;
+        uint2 e = we[0];
+        for (unsigned r0 = 0; r0 < total; r0 += 64 * U) {
+          unsigned kk[U];
+          double vv[U];
+#pragma unroll
+          for (int u = 0; u < U; ++u) {
+            const unsigned r = r0 + u * 64 + lane;
+            vv[u] = 0.0;
+            if (r < total) {
+              while (r >= e.x) e = we[++j];  // r < total = the last end
+              row_in(kb, vb, e.y + r, kk[u], vv[u]);
+            }
+          }
+#pragma unroll
+          for (int u = 0; u < U; ++u)
+            if (r0 + u * 64 + lane < total) feed(kk[u], vv[u]);
+        }
+        __builtin_amdgcn_wave_barrier();
+      }
+    }
   }
   flush();
-  if (((end - a0) & 1) && threadIdx.x == 0) one_row(end - 1);
   __syncthreads();
   if (PART) {
     double2* ps = reinterpret_cast<double2*>(part_sums +
-                                             (int64_t)blockIdx.x * RANGE);
+                                             (int64_t)item * RANGE);
     const double2* ls = reinterpret_cast<const double2*>(lsums);
     for (int s = threadIdx.x; s < RANGE / 2; s += blockDim.x) ps[s] = ls[s];
     if (CNT) {
       uint4* pc = reinterpret_cast<uint4*>(part_cnt +
-                                           (int64_t)blockIdx.x * RANGE);
+                                           (int64_t)item * RANGE);
       const uint4* lc = reinterpret_cast<const uint4*>(lcnt);
       for (int s = threadIdx.x; s < RANGE / 4; s += blockDim.x) pc[s] = lc[s];
     }
     return;
   }
-  const int64_t gbase = (int64_t)w.bucket << RL;
+  const int64_t gbase = (int64_t)bucket << RL;
   for (int s = threadIdx.x; s < RANGE; s += blockDim.x) {
     if (!ltouch[s] || gbase + s >= n_slots) continue;
     if (HAVE_VAL) glob_slot_agg<AOP>(&gsums[gbase + s], lsums[s]);
@@ -3977,8 +4208,17 @@ int ensure_radix_layout(hf_col* keys, int64_t nb) {
 int64_t radix_alloc_rows(const GbKeyCache& kc) {
   return std::max<int64_t>(kc.radix_rows, 64);
 }
+// tiles of a plan (the odd last row is a row of the last tile) and the rows
+// of its tile-major payload
 int64_t gb_plan_tiles(int64_t n) {
-  return ((n & ~1LL) + GB_PLAN_TILE - 1) / GB_PLAN_TILE;
+  return (n + GB_PLAN_TILE - 1) / GB_PLAN_TILE;
+}
+int64_t gb_plan_rows(int64_t n) {
+  return std::max<int64_t>(gb_plan_tiles(n), 1) * GB_PLAN_TILE;
+}
+int64_t gb_item_cut(int64_t n) {
+  return std::min(GB_ITEM_CUT_MAX,
+                  std::max(GB_ITEM_CUT_MIN, n / GB_ITEMS_MIN));
 }
 uint32_t gb_tile_grid(int64_t ntiles) {
   return (uint32_t)std::min<int64_t>(std::max<int64_t>(ntiles, 1), 2048);
@@ -3993,7 +4233,10 @@ enum class GbPlan {
 
 // Valid plan -> Replay, else allocate one -> Record.  HF_GB_PLAN=0 (read
 // once) or a failed plan allocation selects the plan-less path; this never
-// fails the call.
+// fails the call.  Every plan buffer is allocated here, the work items at the
+// bound the histogram gives (a bucket of r rows is cut into at most
+// (r - 1 + ntiles * GB_TILE_COST) / cut + 1 items), so nothing can fail after
+// the record.
 GbPlan ensure_plan(hf_col* keys, int rl, int64_t key_min, int64_t n_slots,
                    int64_t nb) {
   static const bool plan_env = [] {
@@ -4006,18 +4249,31 @@ GbPlan ensure_plan(hf_col* keys, int rl, int64_t key_min, int64_t n_slots,
     return GbPlan::Replay;
   kc.drop_plan();
   const int64_t n = keys->len;
-  DevBuf dst, rk, tab, meta;
-  if (dst.alloc(std::max<int64_t>(n & ~1LL, 2) * 2) != hipSuccess ||
-      rk.alloc(radix_alloc_rows(kc) * 2) != hipSuccess ||
-      tab.alloc(std::max<int64_t>(gb_plan_tiles(n), 1) * (2 * nb + 1) * 4) !=
+  const int64_t cut = gb_item_cut(n);
+  int64_t items_max = 1;
+  for (int64_t b = 0; b < nb; ++b)
+    if (kc.hist[b] > 0)
+      items_max +=
+          (kc.hist[b] - 1 + gb_plan_tiles(n) * GB_TILE_COST) / cut + 1;
+  DevBuf dst, rk, runs, items, item0, order, meta;
+  if (dst.alloc((n + 2) * 2) != hipSuccess ||
+      rk.alloc(gb_plan_rows(n) * 2) != hipSuccess ||
+      runs.alloc(std::max<int64_t>(gb_plan_tiles(n), 1) * nb * 4) !=
           hipSuccess ||
-      meta.alloc(16) != hipSuccess) {
+      items.alloc(items_max * sizeof(GbTileItem)) != hipSuccess ||
+      order.alloc(items_max * 4) != hipSuccess ||
+      // item0[nb + 1], then the per-bucket item counts [nb]
+      item0.alloc((2 * nb + 1) * 4) != hipSuccess ||
+      meta.alloc(8) != hipSuccess) {
     (void)hipGetLastError();
     return GbPlan::None;
   }
   kc.d_plan_dst = dst.release();
   kc.d_plan_rk = rk.release();
-  kc.d_plan_tab = tab.release();
+  kc.d_plan_runs = runs.release();
+  kc.d_plan_items = items.release();
+  kc.d_plan_item0 = item0.release();
+  kc.d_plan_order = order.release();
   kc.d_plan_meta = meta.release();
   return GbPlan::Record;
 }
@@ -4030,16 +4286,18 @@ struct GbRadixCall {
   double* r0;          // scattered values (each column in turn on a plan)
   double* r1;          // second column, plan-less path only
   unsigned short* rk;  // scattered low keys (the plan's own on a plan)
-  unsigned* d_cur;     // this call's bucket cursors (none on replay)
+  unsigned* d_cur;     // this call's bucket cursors (plan-less path only)
+  bool tiled;          // on a plan: tile-major payload, GbTileItem work
 };
 
 // P1 scatter (pipelined): 12288-row tiles as 1024x12 for <=1 value column
 // — 147 KB LDS, 1 block/CU of 16 waves (round-2 probe: 1024x12 edges out
 // 512x24 and both beat the round-1 kernel by ~17%); 6144-row tiles as
 // 512x12 for 2 columns.
-// REC, the plan record: the scatter itself on the int64 keys (no u32 copy),
-// first value column only, at the plan's 1024x12 geometry, keeping its
-// decisions on the key column.
+// REC, the plan record: the same staging on the int64 keys (no u32 copy),
+// first value column only, at the plan's 1024x12 geometry, written tile-major;
+// then the plan's work items are cut on the device and the host reads their
+// count back, once.
 template <int RL, bool REC>
 int radix_scatter(const GbRadixCall& a, const GbPtrs& ptrs, int nvals) {
   GbKeyCache& kc = a.keys->gb;
@@ -4047,9 +4305,8 @@ int radix_scatter(const GbRadixCall& a, const GbPtrs& ptrs, int nvals) {
   GbPlanRec rec{};
   if (REC) {
     unsigned long long* meta = (unsigned long long*)kc.d_plan_meta;
-    HF_HIP("gb_radix", hipMemsetAsync(meta, 0xFF, 8, g.stream));
-    HF_HIP("gb_radix", hipMemsetAsync(meta + 1, 0, 8, g.stream));
-    rec = GbPlanRec{(unsigned short*)kc.d_plan_dst, (unsigned*)kc.d_plan_tab,
+    HF_HIP("gb_radix", hipMemsetAsync(meta, 0, 8, g.stream));
+    rec = GbPlanRec{(unsigned short*)kc.d_plan_dst, (unsigned*)kc.d_plan_runs,
                     meta};
   }
   int rc = with_nvals<(REC ? 1 : 2)>(
@@ -4057,7 +4314,8 @@ int radix_scatter(const GbRadixCall& a, const GbPtrs& ptrs, int nvals) {
         constexpr int NV = decltype(nvTag)::value;
         constexpr int BLK = NV < 2 ? GB_PLAN_BLK : 512;
         constexpr int64_t TILE = (int64_t)BLK * GB_PLAN_RPT;
-        const uint32_t sgrid = gb_tile_grid(((n & ~1LL) + TILE - 1) / TILE);
+        const uint32_t sgrid =
+            gb_tile_grid(((REC ? n : n & ~1LL) + TILE - 1) / TILE);
         const uint32_t lds =
             (uint32_t)(TILE * (8 * NV + 4) + a.nb * 12 + 16);
         return timed_launch(REC ? "gb_plan_record" : "gb_scatter", [&] {
@@ -4069,29 +4327,84 @@ int radix_scatter(const GbRadixCall& a, const GbPtrs& ptrs, int nvals) {
               a.d_err, rec);
         });
       });
-  if (REC && rc == HF_OK) {
-    kc.plan_kmin = a.key_min;
-    kc.plan_nslots = a.n_slots;
-    kc.plan_rl = RL;
+  if (!REC || rc != HF_OK) return rc;
+  unsigned* item0 = (unsigned*)kc.d_plan_item0;
+  unsigned* nitems = item0 + a.nb + 1;
+  const int64_t ntiles = gb_plan_tiles(n);
+  GbTileItem* d_items = (GbTileItem*)kc.d_plan_items;
+  rc = timed_launch("gb_plan_items", [&] {
+    hipLaunchKernelGGL(k_gb_plan_items<false>, dim3((uint32_t)a.nb), dim3(64),
+                       0, g.stream, rec.runs, ntiles, (int)a.nb,
+                       gb_item_cut(n), nitems, item0, d_items);
+  });
+  if (rc != HF_OK) return rc;
+  rc = timed_launch("gb_plan_items", [&] {
+    hipLaunchKernelGGL(k_gb_plan_items<true>, dim3((uint32_t)a.nb), dim3(64),
+                       0, g.stream, rec.runs, ntiles, (int)a.nb,
+                       gb_item_cut(n), nitems, item0, d_items);
+  });
+  if (rc != HF_OK) return rc;
+  unsigned total = 0;
+  HF_HIP("gb_radix", hipMemcpyAsync(&total, item0 + a.nb, 4,
+                                    hipMemcpyDeviceToHost, g.stream));
+  HF_HIP("gb_radix", hipStreamSynchronize(g.stream));
+  // Dispatch order, costliest item first (cost as in the cut: rows +
+  // GB_TILE_COST per tile), so that the kernel's tail is made of its cheapest
+  // items; a few hundred to a few thousand items to sort.
+  if (total > 0) {
+    std::vector<GbTileItem> it(total);
+    HF_HIP("gb_radix", hipMemcpyAsync(it.data(), d_items,
+                                      total * sizeof(GbTileItem),
+                                      hipMemcpyDeviceToHost, g.stream));
+    HF_HIP("gb_radix", hipStreamSynchronize(g.stream));
+    std::vector<int64_t> cost(total);
+    for (unsigned i = 0; i < total; ++i) {
+      const bool last = i + 1 == total || it[i + 1].bucket != it[i].bucket;
+      const int64_t rows =
+          (last ? kc.hist[it[i].bucket] : (int64_t)it[i + 1].row0) -
+          it[i].row0;
+      cost[i] = rows + GB_TILE_COST * (it[i].tile_end - it[i].tile_begin);
+    }
+    std::vector<unsigned> ord(total);
+    for (unsigned i = 0; i < total; ++i) ord[i] = i;
+    std::stable_sort(ord.begin(), ord.end(),
+                     [&](unsigned x, unsigned y) { return cost[x] > cost[y]; });
+    HF_HIP("gb_radix", hipMemcpyAsync(kc.d_plan_order, ord.data(), total * 4,
+                                      hipMemcpyHostToDevice, g.stream));
+    HF_HIP("gb_radix", hipStreamSynchronize(g.stream));
   }
-  return rc;
+  kc.plan_items_n = total;
+  kc.plan_kmin = a.key_min;
+  kc.plan_nslots = a.n_slots;
+  kc.plan_rl = RL;
+  return HF_OK;
+}
+
+// The replay writeout uses non-temporal stores unless HF_GB_NT_STORE=0 (read
+// once; 1 selects them whatever the default), so both flavours can be
+// measured in one build.
+bool gb_replay_nt() {
+  static const bool nt = [] {
+    const char* e = getenv("HF_GB_NT_STORE");
+    return e ? e[0] == '1' : GB_REPLAY_NT_DEFAULT;
+  }();
+  return nt;
 }
 
 // P1 on a recorded plan: the value permutation of one column into r0.
 int radix_replay(const GbRadixCall& a, const double* v, bool add_err) {
   const GbKeyCache& kc = a.keys->gb;
   const int64_t n = a.keys->len;
-  int search0 = 0;  // largest power of two <= nb - 1 (replay's first step)
-  for (int s = 1; s <= a.nb - 1; s <<= 1) search0 = s;
-  const uint32_t lds =
-      (uint32_t)((int64_t)GB_PLAN_TILE * 8 + (2 * a.nb + 1) * 4);
-  return timed_launch("gb_scatter", [&] {
-    hipLaunchKernelGGL((k_gb_replay<GB_PLAN_RPT, GB_PLAN_BLK>),
-                       dim3(gb_tile_grid(gb_plan_tiles(n))), dim3(GB_PLAN_BLK),
-                       lds, g.stream, (const unsigned short*)kc.d_plan_dst, v,
-                       n, (int)a.nb, search0, (const unsigned*)kc.d_plan_tab,
-                       (const unsigned long long*)kc.d_plan_meta, a.r0,
-                       a.d_err, add_err ? 1 : 0);
+  const uint32_t lds = (uint32_t)((int64_t)GB_PLAN_TILE * 8);
+  return with_bool(gb_replay_nt(), [&](auto ntTag) {
+    return timed_launch("gb_scatter", [&] {
+      hipLaunchKernelGGL(
+          (k_gb_replay<GB_PLAN_RPT, GB_PLAN_BLK, decltype(ntTag)::value>),
+          dim3(gb_tile_grid(gb_plan_tiles(n))), dim3(GB_PLAN_BLK), lds,
+          g.stream, (const unsigned short*)kc.d_plan_dst, v, n,
+          (const unsigned long long*)kc.d_plan_meta, a.r0, a.d_err,
+          add_err ? 1 : 0);
+    });
   });
 }
 
@@ -4111,12 +4424,18 @@ template <int RL, int AOP, bool R, bool C, bool V>
 int radix_agg(const GbRadixCall& a, const double* v, double* gs,
               unsigned long long* growcnt, unsigned long long* gc) {
   const GbKeyCache& kc = a.keys->gb;
-  return timed_launch("gb_bucket_agg", [&] {
-    hipLaunchKernelGGL((k_gb_bucket_agg<R, C, V, RL, AOP>),
-                       dim3((uint32_t)kc.work_n), dim3(gb_p2_block(RL)), 0,
-                       g.stream, v,
-                       a.rk, (const GbWorkItem*)kc.d_work, a.n_slots, gs,
-                       growcnt, gc);
+  return with_bool(a.tiled, [&](auto tTag) {
+    constexpr bool T = decltype(tTag)::value;
+    return timed_launch("gb_bucket_agg", [&] {
+      hipLaunchKernelGGL(
+          (k_gb_bucket_agg<R, C, V, RL, AOP, false, T>),
+          dim3((uint32_t)(T ? kc.plan_items_n : kc.work_n)),
+          dim3(gb_p2_block(RL)), 0, g.stream, v, a.rk,
+          T ? (const void*)kc.d_plan_items : (const void*)kc.d_work,
+          a.n_slots, gs, growcnt, gc, nullptr, nullptr,
+          (const unsigned*)kc.d_plan_runs, gb_plan_tiles(a.keys->len),
+          (const unsigned*)kc.d_plan_order);
+    });
   });
 }
 
@@ -4182,12 +4501,12 @@ int gb_radix_mapped(hf_col* keys, const GbPtrs& ptrs, int nvals,
   const int64_t nb = (n_slots + RANGE - 1) >> RL;
   // one partial buffer serves every value column in turn, like r0
   DevBuf r0, part_sums, part_cnt;
-  HF_HIP("hf_groupby_reduce", r0.alloc(radix_alloc_rows(kc) * 8));
-  HF_HIP("hf_groupby_reduce", part_sums.alloc(kc.work_n * RANGE * 8));
+  HF_HIP("hf_groupby_reduce", r0.alloc(gb_plan_rows(keys->len) * 8));
+  HF_HIP("hf_groupby_reduce", part_sums.alloc(kc.plan_items_n * RANGE * 8));
   if (want_counts)
-    HF_HIP("hf_groupby_reduce", part_cnt.alloc(kc.work_n * RANGE * 4));
+    HF_HIP("hf_groupby_reduce", part_cnt.alloc(kc.plan_items_n * RANGE * 4));
   const GbRadixCall a{keys, nb, key_min, n_slots, nullptr, r0.as<double>(),
-                      nullptr, (unsigned short*)kc.d_plan_rk, nullptr};
+                      nullptr, (unsigned short*)kc.d_plan_rk, nullptr, true};
   for (int c = 0; c < nvals; ++c) {
     rc = o.sums[c].alloc(ng, HF_FLOAT64);
     if (rc == HF_OK && want_counts) rc = o.cnts[c].alloc(ng, HF_INT64);
@@ -4197,11 +4516,12 @@ int gb_radix_mapped(hf_col* keys, const GbPtrs& ptrs, int nvals,
       constexpr bool C = decltype(cTag)::value;
       int r = timed_launch("gb_bucket_agg", [&] {
         hipLaunchKernelGGL(
-            (k_gb_bucket_agg<false, C, true, RL, AOP, true>),
-            dim3((uint32_t)kc.work_n), dim3(gb_p2_block(RL)), 0, g.stream,
-            a.r0, a.rk, (const GbWorkItem*)kc.d_work, n_slots, nullptr,
-            nullptr, nullptr,
-            part_sums.as<double>(), part_cnt.as<unsigned>());
+            (k_gb_bucket_agg<false, C, true, RL, AOP, true, true>),
+            dim3((uint32_t)kc.plan_items_n), dim3(gb_p2_block(RL)), 0,
+            g.stream, a.r0, a.rk, (const void*)kc.d_plan_items, n_slots,
+            nullptr, nullptr, nullptr, part_sums.as<double>(),
+            part_cnt.as<unsigned>(), (const unsigned*)kc.d_plan_runs,
+            gb_plan_tiles(keys->len), (const unsigned*)kc.d_plan_order);
       });
       if (r != HF_OK) return r;
       // the compaction of this path, so it keeps that stat name
@@ -4209,7 +4529,8 @@ int gb_radix_mapped(hf_col* keys, const GbPtrs& ptrs, int nvals,
         hipLaunchKernelGGL(
             (k_gb_combine<RL, AOP, C>),
             dim3((uint32_t)((n_slots + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0,
-            g.stream, (const unsigned*)kc.d_gidx, (const unsigned*)kc.d_item0,
+            g.stream, (const unsigned*)kc.d_gidx,
+            (const unsigned*)kc.d_plan_item0,
             part_sums.as<double>(), part_cnt.as<unsigned>(), n_slots,
             o.sums[c].data<double>(),
             C ? o.cnts[c].data<int64_t>() : nullptr);
@@ -4220,9 +4541,10 @@ int gb_radix_mapped(hf_col* keys, const GbPtrs& ptrs, int nvals,
   return HF_OK;
 }
 
-// The radix groupby driver: layout -> plan mode -> P1 -> per column
-// (replay?) -> P2.  Every temporary is scoped, so any early return gives its
-// blocks back to the allocator.
+// The radix groupby driver: plan mode -> (layout) -> P1 -> per column
+// (replay?) -> P2.  The region layout is built only for the plan-less path.
+// Every temporary is scoped, so any early return gives its blocks back to the
+// allocator.
 template <int RL, int AOP>
 int gb_radix_path(hf_col* keys, const GbPtrs& ptrs, int nvals, int64_t key_min,
                   int64_t n_slots, uintptr_t sums, uintptr_t rowcnt,
@@ -4232,21 +4554,20 @@ int gb_radix_path(hf_col* keys, const GbPtrs& ptrs, int nvals, int64_t key_min,
   const int64_t nb = (n_slots + (1 << RL) - 1) >> RL;
   int rc = ensure_host_hist(keys, key_min, n_slots, nb, RL);
   if (rc != HF_OK) return rc;
-  rc = ensure_radix_layout<RL>(keys, nb);
-  if (rc != HF_OK) return rc;
   const GbPlan mode = ensure_plan(keys, RL, key_min, n_slots, nb);
   if (mode == GbPlan::None) {
+    rc = ensure_radix_layout<RL>(keys, nb);
+    if (rc != HF_OK) return rc;
     rc = ensure_keys32(keys, key_min);
     if (rc != HF_OK) return rc;
   }
-  const int64_t rows = radix_alloc_rows(kc);
+  const int64_t rows = mode == GbPlan::None ? radix_alloc_rows(kc)
+                                            : gb_plan_rows(keys->len);
   DevBuf r0, r1, rk, d_cur;
   if (nvals > 0) HF_HIP("gb_radix", r0.alloc(rows * 8));
   if (mode == GbPlan::None) {
     if (nvals > 1) HF_HIP("gb_radix", r1.alloc(rows * 8));
     HF_HIP("gb_radix", rk.alloc(rows * 2));
-  }
-  if (mode != GbPlan::Replay) {
     HF_HIP("gb_radix", d_cur.alloc(nb * 4));
     HF_HIP("gb_radix", hipMemcpyAsync(d_cur.as<void>(), kc.d_curinit, nb * 4,
                                       hipMemcpyDeviceToDevice, g.stream));
@@ -4255,15 +4576,16 @@ int gb_radix_path(hf_col* keys, const GbPtrs& ptrs, int nvals, int64_t key_min,
                       r1.as<double>(),
                       mode == GbPlan::None ? rk.as<unsigned short>()
                                            : (unsigned short*)kc.d_plan_rk,
-                      d_cur.as<unsigned>()};
+                      d_cur.as<unsigned>(), mode != GbPlan::None};
   // P1 (a replayed plan permutes per column, in the P2 loop below)
   if (mode == GbPlan::None)
     rc = radix_scatter<RL, false>(a, ptrs, nvals);
   else if (mode == GbPlan::Record)
     rc = radix_scatter<RL, true>(a, ptrs, nvals);
-  else if (nvals == 0 || kc.work_n == 0)
+  const int64_t work_n = a.tiled ? kc.plan_items_n : kc.work_n;
+  if (rc == HF_OK && mode == GbPlan::Replay && (nvals == 0 || work_n == 0))
     rc = radix_plan_err(a);
-  if (rc != HF_OK || kc.work_n == 0) return rc;
+  if (rc != HF_OK || work_n == 0) return rc;
   // P2 aggregate, one column per launch
   unsigned long long* growcnt = (unsigned long long*)rowcnt;
   if (nvals == 0)
@@ -4607,7 +4929,7 @@ int hf_groupby_reduce(const hf_col* keys, const hf_col* const* vals, int nvals,
   // arm the group map when this call ran on a valid recorded plan; a failed
   // map allocation only leaves the column on this path
   const bool arm = rl != 0 && kc.plan_rl == rl && kc.plan_kmin == key_min &&
-                   kc.plan_nslots == n_slots && kc.work_n > 0 && !kc.d_gidx;
+                   kc.plan_nslots == n_slots && kc.plan_items_n > 0 && !kc.d_gidx;
   if (arm && gidx.alloc(n_slots * 4) != hipSuccess) (void)hipGetLastError();
   hf_col* okeys = nullptr;
   rc = gb_compact((uintptr_t)sums.as<void>(), (uintptr_t)rowcnt.as<void>(),
