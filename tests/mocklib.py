@@ -89,6 +89,13 @@ def install(monkeypatch):
     def gather(col, idx):
         return _reg(MockCol(col.arr[idx.arr]))
 
+    def gather_fill(col, idx, fill):
+        miss = idx.arr < 0
+        out = col.arr[np.where(miss, 0, idx.arr)] if col.arr.size \
+            else np.zeros(idx.arr.size, dtype=col.arr.dtype)
+        out[miss] = fill
+        return _reg(MockCol(out))
+
     def scatter(col, idx):
         out = np.empty_like(col.arr)
         out[idx.arr] = col.arr
@@ -286,11 +293,11 @@ def install(monkeypatch):
 
     def search_sorted(keys, sorted_uniq):
         su = sorted_uniq.arr
+        if not su.size:
+            return _reg(MockCol(np.full(keys.arr.size, -1, dtype=np.int64)))
         pos = np.searchsorted(su, keys.arr)
-        pos = np.clip(pos, 0, max(su.size - 1, 0))
-        hit = su.size > 0
-        out = np.where(hit & (su[pos] == keys.arr) if su.size else False,
-                       pos, -1).astype(np.int64)
+        pos = np.clip(pos, 0, su.size - 1)
+        out = np.where(su[pos] == keys.arr, pos, -1).astype(np.int64)
         return _reg(MockCol(out))
 
     def cross_idx(nl, nr):
@@ -442,6 +449,17 @@ def install(monkeypatch):
         pass
 
     def join_build(rkeys, rvals, key_min, n_slots):
+        # the entry's contract (hf_join_build), with its wording
+        if n_slots > (1 << 27):
+            raise lib.HfError(
+                "hf_join_build: right key range too large for the "
+                "dense-range CSR (hash build is a later round)")
+        slot = rkeys.arr.view(np.uint64) - np.uint64(key_min % 2**64)
+        n_bad = int((slot >= np.uint64(n_slots)).sum())
+        if n_bad:
+            raise lib.HfError(
+                f"hf_join_build: {n_bad} right keys outside "
+                "[key_min, key_min+n_slots)")
         j = _MockJoin()
         j.k = rkeys.arr.copy()
         j.v = [v.arr.copy() for v in rvals]
@@ -456,6 +474,10 @@ def install(monkeypatch):
                              "li": np.arange(lkeys.arr.size)})
         rdf = _pd.DataFrame({"k": j.k, "ri": np.arange(j.k.size)})
         m = ldf.merge(rdf, on="k", how="inner", sort=False)
+        # hf_join_probe's order is left row, then right row within a key;
+        # pandas leaves it when a short left side meets a longer right side
+        # with repeated keys on both
+        m = m.sort_values(["li", "ri"], kind="stable", ignore_index=True)
         keys = _reg(MockCol(m["k"].to_numpy().astype(np.int64)))
         lidx = _reg(MockCol(m["li"].to_numpy().astype(np.int64)))
         ri = m["ri"].to_numpy()
@@ -470,7 +492,8 @@ def install(monkeypatch):
         ("put", put), ("get", get), ("alloc", alloc),
         ("fill_f64", fill_f64), ("fill_i64", fill_i64),
         ("col_slice", col_slice), ("concat", concat), ("gather", gather),
-        ("scatter", scatter), ("sort_perm", sort_perm),
+        ("gather_fill", gather_fill), ("scatter", scatter),
+        ("sort_perm", sort_perm),
         ("fill_randf64", fill_randf64), ("shuffle_dest", shuffle_dest),
         ("cumsum", cumsum), ("seg_cumsum", seg_cumsum),
         ("filter_plan", filter_plan), ("filter_apply", filter_apply),

@@ -21,6 +21,7 @@ import pytest
 
 import oracle
 from modin_amd.core import lib
+from tests.join_ref import inner_join_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -269,14 +270,8 @@ def test_balance_groupby_hash():
 
 def _join_np(lkeys, rkeys, rvals):
     """Inner join, left order then right order within a key."""
-    order = np.argsort(rkeys, kind="stable")
-    srt = rkeys[order]
-    lo = np.searchsorted(srt, lkeys, side="left")
-    hi = np.searchsorted(srt, lkeys, side="right")
-    lidx = np.repeat(np.arange(lkeys.size), hi - lo)
-    ridx = (np.concatenate([order[a:b] for a, b in zip(lo, hi)])
-            if lkeys.size else np.empty(0, dtype=np.int64)).astype(np.int64)
-    return lkeys[lidx], lidx, [v[ridx] for v in rvals]
+    keys, lidx, _ridx, cols = inner_join_ref(lkeys, rkeys, rvals)
+    return keys, lidx, cols
 
 
 def _join_scenario(lkeys, rkeys, rvals, key_min, n_slots):
