@@ -432,7 +432,10 @@ def install(monkeypatch):
                  else np.empty(0, dtype=np.float64))
             m = ~np.isnan(x)
             if agg == 0:
-                sl = np.bincount(inv[m], weights=x[m], minlength=n)
+                # float64 also when nothing was accumulated (an empty
+                # bincount comes back int64)
+                sl = np.bincount(inv[m], weights=x[m],
+                                 minlength=n).astype(np.float64)
             else:
                 ident = np.inf if agg == 1 else -np.inf
                 sl = np.full(n, ident)
